@@ -11,6 +11,17 @@ data-path collective) and the per-point outputs are all-gathered over RCCL.
 The timed region is bracketed by barrier + synchronize on both sides and the
 slowest rank's time is used.  Rank 0 prints ONE JSON line.
 
+A plain run sets up, warms up, times the `--steps` steps and prints the line:
+`value`, `ms_per_step` (milliseconds of one timed step), `step_ms`, `roofline`
+and `kernels` all come from that one timed region.  `--full` adds the legs
+that take runs of their own (marked [full] below); without it they are null.
+
+`--dump-outputs DIR` writes the four head outputs of the timed region's LAST
+step (what a caller of the timed path receives) as DIR/<head>.npy, float32,
+rank 0 only.  Past 64 MB in all, a fixed seeded sample of point positions, the
+same for every head.  The clouds are seeded by scene id, so the same arguments
+give the same inputs in every run.
+
 `python bench.py --gpus N` with N > 1 and no WORLD_SIZE in the environment
 launches itself: the parent starts `python -m torch.distributed.run ... bench.py`
 as a child process BEFORE importing torch or touching a GPU, relays rank 0's
@@ -21,29 +32,30 @@ Extra objects on the line:
   roofline      the dominant kernel of a step: the MFMA shared-MLP contraction (all its
                 launches), HIP-event durations from the timed region, flops the matrix
                 cores execute against the dense peak, PMC traffic from profiles/ (only
-                when it was measured on the same sources and arguments, else null)
-  roofline_ball_query_group_points
+                when it was measured on the same sources and arguments, else null);
+                [full] `without_geometry`: the same launches in a region of their own
+  roofline_ball_query_group_points  [full]
                 the HBM-bound operator pair the north star names, at SA1 size, through
                 the operator API on the same batch (+ the fused single-pass entry point)
   step_ms       per-step completion intervals: median / p10 / p90 / pipeline fill
-  latency       one batch alone (no pipelining) and the one-scene (B = 1) figures
-  io            H2D of the clouds / D2H of the outputs, measured apart (never in `value`)
+  latency       [full] one batch alone (no pipelining) and the one-scene (B = 1) figures
+  io            [full] H2D of the clouds / D2H of the outputs, measured apart (never in `value`)
   kernels       every native launch: mean ms, algorithmic bytes / flops, GB/s / TFLOP/s
-  configs4      BASELINE.json configs[4] (bf16 path, 32 x 51 200-point clouds): scenes/s, ms/step and
+  configs4      [full] BASELINE.json configs[4] (bf16 path, 32 x 51 200-point clouds): scenes/s, ms/step and
                 its own MFMA roofline object, 5 warm + 10 timed steps after the headline region
-  modules_path  the reference-shaped modules over the HIP operators on the same scenes (what swapping
+  modules_path  [full] the reference-shaped modules over the HIP operators on the same scenes (what swapping
                 only the extension buys), scenes/s
-  precision_legs  the fast path in true-fp32 MFMA and exact 3 x bf16 arithmetic on the same batch
-  detect        the reference's production entry GraspDetector.detect composed on the device (detector.py): raw clouds in,
+  precision_legs  [full] the fast path in true-fp32 MFMA and exact 3 x bf16 arithmetic on the same batch
+  detect        [full] the reference's production entry GraspDetector.detect composed on the device (detector.py): raw clouds in,
                 selected grasp poses out; scenes/s pipelined at the step's batch, per-stage ms, one-scene latency (eager / graph)
-  weights_leg   the same step on the other network (--weights: `calibrated` is the default and the headline; `randomized`
+  weights_leg   [full] the same step on the other network (--weights: `calibrated` is the default and the headline; `randomized`
                 is what rounds 1-5 timed)
-  mixed_batch   2 of the 16 scenes tie-heavy: the conditional level-2 / level-3 FPS samplers run timed
-  kept_points   clouds in, 50 grasp frames per scene out with the pose heads evaluated on the 2 048 best-scoring points
+  mixed_batch   [full] 2 of the 16 scenes tie-heavy: the conditional level-2 / level-3 FPS samplers run timed
+  kept_points   [full] clouds in, 50 grasp frames per scene out with the pose heads evaluated on the 2 048 best-scoring points
                 per scene only (FusedPointNet2(..., topk=)), next to the full forward + decode; NOT the headline
   collective    the per-batch all-gather: payload (--gather heads | poses), bytes, the stream it ran on
   distributed   world, communicator size, every rank's scene range and device (self-verifying)
-  cpu_baseline  the CPU oracle forward (oracle/pn2_forward.py) on ONE scene,
+  cpu_baseline  [full] the CPU oracle forward (oracle/pn2_forward.py) on ONE scene,
                 rank 0 at N == 1 only -- a reported baseline, not the target
 
 TEST MODE (tests/test_bench_world.py only): S4G_BENCH_BACKEND=gloo runs this file's whole control flow --
@@ -89,9 +101,15 @@ def parse(argv=None):
     ap.add_argument("--batch", type=int, default=16, help="scenes per GPU per step")
     ap.add_argument("--points", type=int, default=25600)
     ap.add_argument("--impl", default="auto", choices=["auto", "fused", "modules"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region, also run the legs that take runs of their own (latency / io / "
+                         "operator-pair probes, configs[4], the other paths, precisions and networks, the CPU "
+                         "baseline); a plain run times the steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the head outputs of the last timed step to DIR/<head>.npy (float32, rank 0)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--no-extras", action="store_true",
-                    help="skip the latency / io / operator-pair probes after the timed region")
+                    help="with --full: skip the latency / io / operator-pair probes after the timed region")
     ap.add_argument("--in-flight", type=int, default=2,
                     help="batches kept in flight besides the one being collected")
     ap.add_argument("--no-pipeline", action="store_true",
@@ -110,7 +128,7 @@ def parse(argv=None):
                          "pair around EVERY launch the step measured 9.04 ms against 8.85 ms at k = 4 and "
                          "8.84 ms with none, profiles/r03_timer_sampling.md)")
     ap.add_argument("--no-configs4", action="store_true",
-                    help="skip the configs[4] (bf16, 51 200 points, 32 scenes) leg after the timed region")
+                    help="with --full: skip the configs[4] (bf16, 51 200 points, 32 scenes) leg after the timed region")
     ap.add_argument("--weights", default="calibrated", choices=["calibrated", "randomized"],
                     help="the network the step is timed on: 'calibrated' (default) = the golden run's network "
                          "(tests/golden/pn2_calib_full.npz: seeded convolutions, BatchNorm statistics calibrated through "
@@ -250,6 +268,29 @@ class _HostRank:
 
     def init_kw(self):
         return {"backend": "gloo"}
+
+
+DUMP_LIMIT_BYTES = 63 * 10 ** 6      # --dump-outputs: at most 64 MB on disk, .npy headers included
+
+
+def dump_outputs(pred, heads, out_dir):
+    """--dump-outputs: the head tensors of one step as out_dir/<head>.npy, float32.  Past DUMP_LIMIT_BYTES in all,
+    the same seeded sample of point positions (last axis) is kept for every head, so runs with the same arguments
+    stay comparable element for element."""
+    import numpy as np
+    arrs = {k: pred[k].detach().float().cpu().numpy() for k in heads}
+    total = sum(a.nbytes for a in arrs.values())
+    n = arrs[heads[0]].shape[-1]
+    sample = None
+    if total > DUMP_LIMIT_BYTES:
+        keep = max(1, n * DUMP_LIMIT_BYTES // total)
+        sample = np.sort(np.random.default_rng(0).choice(n, keep, replace=False))
+        arrs = {k: np.ascontiguousarray(a[..., sample]) for k, a in arrs.items()}
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrs.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a)
+    return {"dir": out_dir, "files": sorted(k + ".npy" for k in arrs), "dtype": "float32",
+            "points_kept": n if sample is None else int(sample.size), "points": n}
 
 
 def percentile(xs, q):
@@ -406,6 +447,7 @@ def main():
         gather = sdist.OutputGather(args.gather, decode=decode, device=dev)
 
     solo = [False]    # set once the other ranks have left: nothing after that may enter a collective
+    last_pred = [None]    # the outputs of the most recently collected step (--dump-outputs)
 
     def run_steps(n, run=None, data=None, pipe=None, marks=None, gathered=True):
         """n forward passes over the batch.  Pipelined mode keeps up to `--in-flight`
@@ -418,8 +460,12 @@ def main():
         data = batch if data is None else data
         pipe = pipelined if pipe is None else pipe
         assert not (solo[0] and gathered and gather is not None), "all-gather inside a rank-0-only leg"
-        fin = (lambda pred: gather(pred, data["scene_points"])) if (gathered and gather is not None) \
-            else (lambda pred: pred)
+
+        def fin(pred):
+            last_pred[0] = pred
+            if gathered and gather is not None:
+                return gather(pred, data["scene_points"])
+            return pred
 
         def mark():
             if marks is not None:
@@ -499,6 +545,8 @@ def main():
             dist.destroy_process_group()
         return
     solo[0] = True
+    # before any leg of --full runs: the timed path's outputs of its last step
+    dumped = dump_outputs(last_pred[0], heads, args.dump_outputs) if args.dump_outputs else None
 
     scenes = world * B * args.steps
     value = scenes / elapsed
@@ -509,7 +557,7 @@ def main():
     roofline = latency = io = configs4 = modules_path = precision_legs = mixed_batch = kept_points = weights_leg = detect_leg = None
     # (the single-GPU probes below run at N = 1 only: at N > 1 the other ranks have left, rank 0 prints its line
     #  and tears the communicator down without making the job wait for figures the N = 1 line already carries)
-    if not args.no_extras and world == 1:
+    if args.full and not args.no_extras and world == 1:
         # ---- one batch alone / one scene: the figures the pipeline hides
         def timed_forward(data, reps):
             ts = []
@@ -841,7 +889,7 @@ def main():
         roofline_dense["traffic_note"] = why
 
     cpu_baseline = None
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         from oracle import oracle as _oracle
         from oracle import pn2_forward
         ncores = os.cpu_count() or 1
@@ -943,6 +991,7 @@ def main():
         "weights_leg": weights_leg, "detect": detect_leg, "mixed_batch": mixed_batch, "kept_points": kept_points, "collective": collective, "distributed": shards,
         "step_ms": step_ms, "latency": latency, "io": io, "kernels": kernels,
         "cpu_baseline": cpu_baseline,
+        **({"dumped_outputs": dumped} if dumped else {}),
     }
     print(json.dumps(line))
     if use_dist:

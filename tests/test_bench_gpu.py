@@ -1,4 +1,4 @@
-"""bench.py contract: ONE JSON line with the keys the driver reads (GPU box only)."""
+"""bench.py contract: ONE JSON line with the keys the driver reads (GPU only)."""
 import json
 import os
 import subprocess
@@ -12,7 +12,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 def test_bench_prints_one_contract_line():
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3",
-                          "--warmup", "1"], capture_output=True, text=True, timeout=600, cwd=ROOT)
+                          "--warmup", "1", "--full"], capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.strip()]
     assert len(lines) == 1, lines
@@ -82,7 +82,7 @@ def test_bench_under_torchrun_takes_the_rccl_path():
     out = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1",
                           "--nproc-per-node", "1", "--master-addr", "127.0.0.1", "--master-port",
                           "29517", os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3",
-                          "--warmup", "1", "--no-cpu-baseline"],
+                          "--warmup", "1", "--no-cpu-baseline", "--full"],
                          capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.strip().startswith("{")]
@@ -116,3 +116,36 @@ def test_bench_gather_poses_over_rccl():
     assert c["payload"] == "poses" and c["payload_bytes_per_rank_per_step"] == 16 * 50 * 18 * 4
     assert "decoded grasp frames" in d["config"]["parallelism"] and d["value"] > 0
     assert "all-gather" in d["config"]["parallelism"]
+
+
+def test_plain_bench_times_only_its_steps_and_dumps_what_the_timed_path_computed(tmp_path, dev):
+    """A plain run (no --full): the headline region alone, `--steps` timed steps, the --full legs null; the dumped
+    head outputs of its last step are what the same network computes for the same seeded scenes in this process."""
+    import numpy as np
+    import torch
+    from s4g_release_amd import synth
+    from s4g_release_amd.fused import FusedPointNet2
+    from tests import golden_util as GU
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "5",
+                          "--warmup", "1", "--dump-outputs", str(tmp_path)],
+                         capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [l for l in out.stdout.splitlines() if l.strip()]
+    assert len(lines) == 1, lines
+    d = json.loads(lines[0])
+    assert d["steps"] == 5 and d["step_ms"]["n"] == 4 and abs(d["value"] - 16 * 1e3 / d["ms_per_step"]) < 1e-2 * d["value"]
+    assert d["dtype"] == "f32 (f16x2 split)" and d["roofline"]["bound"] == "mfma"
+    for k in ("roofline_ball_query_group_points", "latency", "io", "configs4", "modules_path", "precision_legs",
+              "detect", "weights_leg", "mixed_batch", "kept_points", "cpu_baseline"):
+        assert d[k] is None, k
+    assert "without_geometry" not in d["roofline"]
+    runner = FusedPointNet2(GU.calib_full_model().to(dev).eval())
+    pts = torch.from_numpy(synth.make_batch(list(range(16)), 25600, variant="tabletop-v1")).to(dev)
+    with torch.no_grad():
+        pred = runner({"scene_points": pts})
+    for k in ("score", "frame_R", "frame_t", "movable_logits"):
+        got = np.load(str(tmp_path / (k + ".npy")))
+        want = pred[k].cpu().numpy()
+        assert got.dtype == np.float32 and got.shape == want.shape == (16, got.shape[1], 25600), k
+        assert float(np.abs(got - want).max()) <= 1e-5 * max(1.0, float(np.abs(want).max())), k
+        assert float(got.std(axis=2).min()) > 0, k              # outputs that depend on the point

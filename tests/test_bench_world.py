@@ -108,3 +108,53 @@ def test_without_the_test_backend_bench_needs_a_gpu():
     proc = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "1", "--warmup", "0"],
                           env=env, cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=300)
     assert proc.returncode != 0 and "needs a GPU" in proc.stderr and proc.stdout.strip() == ""
+
+
+def test_dump_outputs_writes_the_last_timed_step_of_rank_0(tmp_path):
+    """`--dump-outputs DIR`: rank 0's four head tensors of the last timed step, float32, as DIR/<head>.npy -- here
+    the stub's fill pattern of rank 0's own scenes; `--steps` is the number of timed steps; a plain run carries
+    none of the --full legs."""
+    import numpy as np
+    import torch
+    from s4g_release_amd import synth
+    from tests.bench_stub import CHANNELS, outputs_of
+    steps, batch, points = 4, 3, 200
+    line = _one_line(_bench(["--gpus", "2", "--steps", str(steps), "--warmup", "1", "--batch", str(batch),
+                             "--points", str(points), "--dump-outputs", str(tmp_path)]))
+    assert line["steps"] == steps and line["step_ms"]["n"] == steps - 1
+    assert abs(line["ms_per_step"] - 1e3 * 2 * batch / line["value"]) < 0.01 * line["ms_per_step"]
+    for k in ("roofline_ball_query_group_points", "latency", "io", "configs4", "modules_path", "precision_legs",
+              "detect", "weights_leg", "mixed_batch", "kept_points", "cpu_baseline"):
+        assert line[k] is None, k
+    want = outputs_of(torch.from_numpy(synth.make_batch(list(range(batch)), points))).numpy()
+    heads = ("score", "frame_R", "frame_t", "movable_logits")
+    assert sorted(line["dumped_outputs"]["files"]) == sorted(h + ".npy" for h in heads)
+    for h, w in zip(heads, np.split(want, np.cumsum(CHANNELS)[:-1], axis=1)):
+        got = np.load(str(tmp_path / (h + ".npy")))
+        assert got.dtype == np.float32 and np.array_equal(got, w), h
+
+
+def test_dump_outputs_past_64_mb_is_the_same_seeded_sample_in_every_run(tmp_path):
+    """Outputs larger than 64 MB are written as a fixed sample of point positions: within the limit, the same
+    positions for every head, identical from run to run."""
+    import numpy as np
+    import torch
+    from s4g_release_amd import synth
+    from tests.bench_stub import outputs_of
+    batch, points = 16, 50000                     # 16 x 21 x 50 000 x 4 B = 67 MB
+    runs = []
+    for r in range(2):
+        d = tmp_path / str(r)
+        line = _one_line(_bench(["--gpus", "1", "--steps", "1", "--warmup", "0", "--batch", str(batch),
+                                 "--points", str(points), "--dump-outputs", str(d)]))
+        assert line["dumped_outputs"]["points"] == points
+        runs.append({f.name: np.load(str(f)) for f in sorted(d.iterdir())})
+    assert sum(f.stat().st_size for f in (tmp_path / "0").iterdir()) <= 64 * 10 ** 6
+    assert runs[0].keys() == runs[1].keys() and all(np.array_equal(runs[0][k], runs[1][k]) for k in runs[0])
+    kept = runs[0]["score.npy"].shape[-1]
+    assert 0.9 * points < kept < points and all(a.shape[-1] == kept for a in runs[0].values())
+    # the kept positions are columns of the full output, in order, the same columns for every head
+    full = outputs_of(torch.from_numpy(synth.make_batch(list(range(batch)), points))).numpy()
+    dumped = np.concatenate([runs[0][h + ".npy"] for h in ("score", "frame_R", "frame_t", "movable_logits")], axis=1)
+    cols = [int(np.flatnonzero(np.all(full == dumped[:, :, i:i + 1], axis=(0, 1)))[0]) for i in range(0, kept, 997)]
+    assert cols == sorted(set(cols))

@@ -36,8 +36,8 @@ $R/tools/micro/mfma_ceiling 1.5 > $O/mfma_ceiling.md 2>&1
 python3 $R/tools/power_probe.py --seconds 1.5 > $O/power_clock_default.md 2>/dev/null
 python3 $R/tools/power_probe.py --seconds 1.5 --points 51200 --batch 32 --precision bf16 > $O/power_clock_cfg4.md 2>/dev/null
 # un-profiled lines of the same build, for the record
-python3 $R/bench.py --steps 20 --warmup 5 > $O/bench_default.json 2>/dev/null
-python3 $R/bench.py $CFG4 --steps 30 --warmup 3 --no-cpu-baseline > $O/bench_cfg4.json 2>/dev/null
+python3 $R/bench.py --full --steps 20 --warmup 5 > $O/bench_default.json 2>/dev/null
+python3 $R/bench.py $CFG4 --full --steps 30 --warmup 3 --no-cpu-baseline > $O/bench_cfg4.json 2>/dev/null
 # keep only what the summaries need (the raw trace databases are large)
 find $O -name "*.db" -delete
 find $O -name "*kernel_trace.csv" -delete

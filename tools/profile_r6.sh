@@ -45,8 +45,8 @@ rocprofv3 --kernel-trace --stats -d $O/stats_detect -o run -- python3 $R/tools/d
 db=$(find $O/stats_detect -name "*.db" | head -1)
 [ -n "$db" ] && python3 $R/tools/rocpd_summary.py $db 40 > $O/detect_kernel_stats.md
 # un-profiled lines of the same build, for the record
-python3 $R/bench.py --steps 20 --warmup 5 > $O/bench_default.json 2>/dev/null
-python3 $R/bench.py $CFG4 --steps 30 --warmup 3 --no-cpu-baseline > $O/bench_cfg4.json 2>/dev/null
+python3 $R/bench.py --full --steps 20 --warmup 5 > $O/bench_default.json 2>/dev/null
+python3 $R/bench.py $CFG4 --full --steps 30 --warmup 3 --no-cpu-baseline > $O/bench_cfg4.json 2>/dev/null
 # keep only what the summaries need (the raw trace databases are large)
 find $O -name "*.db" -delete
 find $O -name "*kernel_trace.csv" -delete
