@@ -70,6 +70,10 @@ __global__ __launch_bounds__(64) void decode_pose_kernel(
   float y0 = r[1], y1 = r[4], y2 = r[7];
   const float d = x0 * y0 + x1 * y1 + x2 * y2;
   y0 -= d * x0; y1 -= d * x1; y2 -= d * x2;
+  // second projection: for nearly parallel columns (angle a) the first leaves x.y ~ eps / sin(a) (3e-5 at a = 1e-2);
+  // repeating it brings x.y back to rounding level
+  const float d2 = x0 * y0 + x1 * y1 + x2 * y2;
+  y0 -= d2 * x0; y1 -= d2 * x1; y2 -= d2 * x2;
   const float yn = sqrtf(y0 * y0 + y1 * y1 + y2 * y2);
   y0 /= yn; y1 /= yn; y2 /= yn;
   const float z0 = x1 * y2 - x2 * y1, z1 = x2 * y0 - x0 * y2, z2 = x0 * y1 - x1 * y0;
@@ -142,6 +146,9 @@ __global__ __launch_bounds__(256) void collision_counts_kernel(
   const float* px = xyz + (size_t)b * 3 * N;
   const int nc = (N + COLL_CHUNKS - 1) / COLL_CHUNKS;
   const int i_lo = chunk * nc, i_hi = min(N, i_lo + nc);
+  // an empty chunk (whenever 7 * nc >= N the last chunk(s) get no points: N = 1..7, 9..14, ..., 49): nothing to count;
+  // `counts` is pre-zeroed by the launcher.  chunk = blockIdx.y, so the exit is workgroup-uniform (before any barrier).
+  if (i_lo >= i_hi) return;
   int kmax = K;
   if (pose_count) kmax = (int)min((int64_t)K, max((int64_t)0, pose_count[b]));   // padding rows: never scanned (counts pre-zeroed)
   // this workgroup's poses: k = blockIdx.x + COLL_GX * j, j = 0, 1, ... ; COLL_SLOTS of them per pass
@@ -182,7 +189,7 @@ __global__ __launch_bounds__(256) void collision_counts_kernel(
       for (int u = 0; u < COLL_U; ++u) {
         const int i = i0 + 256 * u;
         in[u] = i < i_hi;
-        const int ii = in[u] ? i : i_lo;
+        const int ii = in[u] ? i : i_hi - 1;         // masked lanes load the chunk's last point (always < N)
         x[u] = px[ii];
         y[u] = px[N + ii];
         z[u] = px[2 * (size_t)N + ii];

@@ -225,12 +225,26 @@ class _Pending:
 class GraphedDetect:
     """`GraspDetector.detect_device` for a fixed cloud shape and fixed thresholds as ONE HIP graph: pre-processing,
     the ~45 launches of the forward, decode, collision check and sampling replayed by a single host call (the
-    one-scene serving latency).  The returned tensors are the graph's static outputs (valid until the next replay)."""
+    one-scene serving latency).  The returned tensors are the graph's static outputs (valid until the next replay).
+
+    The graph reads, by address, device tensors that live in two bounded caches: the subsample index
+    (`GraspDetector._idx_cache`, 8 entries) and the small constants of `detect_poses` (`postprocess._SMALL_LRU`, 16
+    entries).  Eager calls between capture and replay can evict them, and the allocator would then hand their blocks to
+    new tensors under the graph.  So right after the capture (which has just used them; nothing runs in between), the
+    current entries of both caches are referenced here (`self._held`) for the graph's lifetime.  So are the call's
+    keyword arguments (`self._kw`): a device tensor among them (`uniforms`, `collision_cloud`) is read by address too.
+    Host `uniforms` are copied to the device once, before the warm-up, so that the capture records no copy from host
+    memory that is gone by the replay."""
 
     def __init__(self, det, example, kw):
         cloud = _F._f32c(example, "cloud")
         self.static_in = cloud.clone()
         dev = cloud.device
+        kw = dict(kw)
+        u = kw.get("uniforms")
+        if u is not None and not (isinstance(u, torch.Tensor) and u.device == dev):
+            kw["uniforms"] = torch.as_tensor(u, dtype=torch.float64).to(dev)
+        self._kw = kw
         side = torch.cuda.Stream(device=dev)
         side.wait_stream(torch.cuda.current_stream(dev))
         with torch.cuda.stream(side):          # warm-up off the capture: constants, allocator pools, index cache
@@ -246,6 +260,11 @@ class GraphedDetect:
                 self.static_out = det.detect_device(self.static_in, **kw)
         finally:
             _F.OpTimer.enabled, det.stage_events = was, ev
+        with det._lock:
+            held = list(det._idx_cache.values())
+        with _post._SMALL_LOCK:
+            held += list(_post._SMALL_LRU.values())
+        self._held = held
 
     def __call__(self, cloud):
         if tuple(cloud.shape) != tuple(self.static_in.shape):

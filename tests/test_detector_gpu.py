@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 import torch
 
+from tests import collision_ref as CR
 from tests import golden_util as GU
 
 pytestmark = pytest.mark.gpu
@@ -64,7 +65,7 @@ def test_detect_equals_the_oracle_stage_by_stage(dev, n):
     # the candidates BEFORE the collision check, recomputed by the standalone stage (itself checked against the oracle)
     pre = PP.detect_poses(det.run({"scene_points": torch.from_numpy(pts).to(dev)}, topk=K), torch.from_numpy(pts).to(dev),
                           thr, vthr, direction_matrix=dm, frame=PP.TRAIN2REAL, max_poses=K)
-    ok_dev, _ = PP.view_non_collision(pre[0], d_cloud, inverse="se3")
+    ok_dev, counts_dev = PP.view_non_collision(pre[0], d_cloud, inverse="se3")
     for b in range(2):
         rH, rs, ridx = OP.detector_post_processing({k: v[b] for k, v in pred.items()}, pts[b], thr, vthr, dm)
         m = int(pre[3][b])
@@ -76,6 +77,15 @@ def test_detect_equals_the_oracle_stage_by_stage(dev, n):
                                        global2local=OP.se3_inverse_f32(rH)[None])
         okb = ok_dev[b, :m].cpu().numpy()
         assert (okb == rok[0]).mean() >= 0.95                      # (a count at its threshold may differ by an ulp-close point)
+        # the device counts themselves (K ~ 600: the kernel's second pass over poses) against float64 on the same SE(3)
+        # inverse: off by at most the points within 4e-6 of a deciding face, verdicts equal wherever that margin does
+        # not straddle the threshold
+        c64, amb = CR.classify64(PP.se3_inverse(pre[0][b, :m]), d_cloud[b], det.gripper, tol=4e-6)
+        cb = counts_dev[b, :m].cpu().numpy().astype(np.int64)
+        assert (np.abs(cb - c64) <= amb).all(), np.argwhere(np.abs(cb - c64) > amb)[:5]
+        cthr = np.array([det.gripper.back_collision_threshold, det.gripper.finger_collision_threshold])
+        settled = ((c64 - amb <= cthr) == (c64 + amb <= cthr)).all(axis=1)
+        assert np.array_equal(okb[settled], CR.verdicts(c64, det.gripper)[settled]) and settled.mean() > 0.9
         keep = np.nonzero(okb)[0]
         c = int(cnt[b])
         assert c == len(keep) and np.array_equal(index[b, :c], ridx[keep])             # survivors, order kept
@@ -135,6 +145,72 @@ def test_batch_graph_mask_and_reference_signature(dev):
     det.stage_events = None
     assert list(ms) == ["pre_processing", "prediction", "post_processing", "collision_check", "importance_sampling"]
     assert all(v >= 0 for v in ms.values())
+
+
+def test_graph_replay_survives_cache_churn(dev):
+    """`GraphedDetect` holds the device tensors its graph reads by address: the subsample index and the direction
+    matrix (entries of two bounded caches) and the caller's `uniforms`.  Eager calls evict both cache entries (other
+    cloud sizes and seeds; 17 other direction matrices) and the caller drops its `uniforms`: all three tensors must
+    still be alive (weak references, after a garbage collection -- deterministic, whatever the allocator would do with
+    a freed block), and a replay after zero-filled allocations of the same sizes gives bit-identical outputs.  Host
+    `uniforms` give the same detections as the same draws on the device.  (The churned clouds are no larger than the
+    captured one: a stale index would still be in range.)"""
+    import gc
+    import weakref
+    from s4g_release_amd import postprocess as PP
+    from s4g_release_amd.detector import GraspDetector
+    net = GU.shipped_net(dev)
+    cam = np.eye(4)
+    cam[:3, :3] = np.linalg.qr(np.random.default_rng(2).standard_normal((3, 3)))[0]
+    det = GraspDetector(net, topk=K, camera2base=cam, seed=1)
+    n = 30000
+    d = torch.from_numpy(_clouds(n, [5])).to(dev)
+    # the direction matrix matters at this threshold; the draws of the importance sampling are a device tensor the
+    # graph reads (drawn inside the graph, they would differ from replay to replay)
+    draws = [0.1, 0.3, 0.5, 0.7, 0.9]
+    u = torch.tensor(draws, dtype=torch.float64, device=dev)
+    kw = dict(num_selected=5, score_threshold=0.6, verticalness_threshold=0.0)
+    g = det.graph(d, uniforms=u, **kw)
+    out = g(d)
+    torch.cuda.synchronize()
+    want = [t.clone() for t in out] + [t.clone() for t in out.candidates]
+    assert int(want[-1][0]) > 5
+    idx_key = (n, (1,), str(d.device))
+    dm_vals = tuple(v for row in det.direction_matrix for v in row)
+    cached = lambda: (idx_key in det._idx_cache, any(k[0] == dm_vals for k in PP._SMALL_LRU))
+    assert cached() == (True, True)
+    dm_t = next(v for k, v in PP._SMALL_LRU.items() if k[0] == dm_vals)
+    refs = [weakref.ref(det._idx_cache[idx_key]), weakref.ref(dm_t), weakref.ref(u)]
+    del dm_t
+    for i in range(10):
+        det.detect_device(d[:, :, :n - 997 * (i + 1)].contiguous(), seed=100 + i, uniforms=u, **kw)
+    rng = np.random.default_rng(3)
+    m = 256
+    pred = {"score": torch.randn(1, 3, m, device=dev), "frame_R": torch.randn(1, 9, m, device=dev),
+            "frame_t": torch.randn(1, 4, m, device=dev)}
+    pts = torch.randn(1, 3, m, device=dev)
+    for i in range(17):
+        dm = np.linalg.qr(rng.standard_normal((3, 3)))[0]
+        PP.detect_poses(pred, pts, 0.5, 0.0, direction_matrix=dm, max_poses=64)
+    torch.cuda.synchronize()
+    del u
+    gc.collect()
+    assert cached() == (False, False)                     # both entries the graph was captured with are evicted ...
+    assert [r() is not None for r in refs] == [True, True, True]      # ... and, like the dropped draws, still held
+    fill = [torch.zeros((1, det.num_input), dtype=torch.int64, device=dev) for _ in range(16)] + \
+           [torch.zeros(sh, dtype=torch.float32, device=dev) for sh in ((3, 3), (3,), (4, 4)) for _ in range(32)] + \
+           [torch.zeros(5, dtype=torch.float64, device=dev) for _ in range(8)]
+    torch.cuda.synchronize()
+    out = g(d)
+    torch.cuda.synchronize()
+    for x, y in zip(list(out) + list(out.candidates), want):
+        assert torch.equal(x, y)
+    del fill
+    # host draws: copied to the device before the capture, the same detections
+    out = det.graph(d, uniforms=np.array(draws), **kw)(d)
+    torch.cuda.synchronize()
+    for x, y in zip(list(out) + list(out.candidates), want):
+        assert torch.equal(x, y)
 
 
 def test_intended_preprocessing_mode_runs_the_voxel_and_outlier_passes(dev):

@@ -4,6 +4,8 @@ import numpy as np
 import pytest
 import torch
 
+from tests import collision_ref as CR
+
 pytestmark = pytest.mark.gpu
 
 
@@ -62,31 +64,14 @@ def test_batched_collision_check_matches_oracle(dev):
     # face (the 4x4 . 4xN product is summed in a different order on the two sides): classify the
     # points in float64 and count, per pose and per counter, those closer than `tol` to any face
     # that decides the counter -- the two counts may differ by at most that many.
-    g = OP_gripper = dict(hbw=0.057, bl=0.16, fw=0.023, hht=0.012, fl=0.09, margin=0.0)
-    hbs = g["hbw"] - g["fw"]
-    tol = 4e-6
-    Hn = H.cpu().numpy().astype(np.float64)
-    explained = 0
-    for b in range(B):
-        homo = np.concatenate([pts[b].astype(np.float64), np.ones((1, N))], 0)
-        for k in range(K):
-            loc = np.linalg.inv(Hn[b, k]).astype(np.float32).astype(np.float64) @ homo
-            x, y, z = loc[0], loc[1], loc[2]
-            near = lambda v, faces: np.min(np.abs(v[None, :] - np.array(faces)[:, None]), axis=0) < tol
-            inside = lambda v, lo, hi: (v > lo - tol) & (v < hi + tol)
-            region = inside(x, -g["bl"], g["fl"]) & inside(z, -g["hht"], g["hht"]) & inside(y, -g["hbw"], g["hbw"])
-            amb_back = region & (near(x, [g["fl"], -g["bl"], -g["margin"]]) | near(y, [g["hbw"], -g["hbw"]]) |
-                                 near(z, [g["hht"], -g["hht"]]))
-            amb_fing = region & (near(x, [g["fl"], -g["bl"]]) | near(y, [g["hbw"], -g["hbw"], hbs, -hbs]) |
-                                 near(z, [g["hht"], -g["hht"]]))
-            for c, amb in ((0, amb_back), (1, amb_fing)):
-                diff = abs(int(counts_np[b, k, c]) - int(rcounts[b, k, c]))
-                assert diff <= int(amb.sum()), (b, k, c, diff, int(amb.sum()))
-                explained += diff
-            if ok_np[b, k] != rok[b, k]:     # only when a count sits at its threshold, give or take the ambiguous points
-                at_edge = (abs(rcounts[b, k, 0] - 10 * np.sqrt(8)) <= amb_back.sum() + 1) or \
-                          (abs(rcounts[b, k, 1] - 10) <= amb_fing.sum() + 1)
-                assert at_edge, (b, k, counts_np[b, k], rcounts[b, k])
+    amb = CR.classify64(np.linalg.inv(H.cpu().numpy().astype(np.float64)).astype(np.float32), pts,
+                        PP.GripperConfig(), tol=4e-6)[1]
+    diff = np.abs(counts_np - rcounts)
+    assert (diff <= amb).all(), np.argwhere(diff > amb)[:5]
+    # verdicts differ only when a count sits at its threshold, give or take the ambiguous points
+    at_edge = (np.abs(rcounts[..., 0] - 10 * np.sqrt(8)) <= amb[..., 0] + 1) | \
+              (np.abs(rcounts[..., 1] - 10) <= amb[..., 1] + 1)
+    assert (at_edge | (ok_np == rok)).all(), np.argwhere(~at_edge & (ok_np != rok))[:5]
     assert (ok_np == rok).mean() >= 0.95
     assert counts.cpu().numpy().sum() > 0          # the gripper does touch the table-top cloud
 
@@ -251,3 +236,103 @@ def test_demo_decode_and_filter_equal_the_reference(dev, case):
     both = got_ok & ref_ok
     assert np.allclose(s[0].cpu().numpy()[both], ref_s[np.isin(ref_idx, oi[0][both])], atol=1e-6)
     assert np.allclose(H[0].cpu().numpy()[both], ref_H[np.isin(ref_idx, oi[0][both])], atol=3e-5)
+
+
+# ---- expected score and pose decode at their edges: tail blocks (N not a multiple of 256, K not a multiple of 64),
+# C = 1 .. 8 classes, logits that overflow a softmax without the max subtracted, ties, 1 .. 4 t bins, nearly parallel
+# frame columns of any magnitude; all against float64 restatements
+
+@pytest.mark.parametrize("C", [1, 2, 3, 5, 8])
+def test_expected_score_edges(dev, C):
+    from s4g_release_amd import postprocess as PP
+    rng = np.random.default_rng(C)
+    worst = 0.0
+    for B in (1, 4):
+        for N in (1, 255, 256, 257, 25600):
+            lg = rng.standard_normal((B, C, N)) * 3
+            big = rng.random((B, N)) < 0.3                                       # logits up to +-1e3
+            lg = np.where(big[:, None], rng.uniform(-1e3, 1e3, (B, C, N)), lg)
+            tie = rng.random((B, N)) < 0.1                                       # every class the same logit
+            lg = np.where(tie[:, None], rng.choice([-1e3, -7.5, 0.0, 1e3], (B, 1, N)), lg)
+            if C > 1:                                                            # two tied maxima
+                two = rng.random((B, N)) < 0.1
+                top = lg.max(axis=1) + rng.uniform(0, 1e3, (B, N))
+                lg[:, 0] = np.where(two, top, lg[:, 0])
+                lg[:, C - 1] = np.where(two, top, lg[:, C - 1])
+            lg = lg.astype(np.float32)
+            for convention in ("demo", "detector"):
+                got = PP.expected_score(torch.from_numpy(lg).to(dev), convention).cpu().numpy().astype(np.float64)
+                v = np.linspace(0, 1, C + 1)
+                v = v[:-1] if convention == "demo" else v[1:]
+                ref = (torch.softmax(torch.from_numpy(lg).double(), dim=1).numpy() * v[None, :, None]).sum(1)
+                assert np.isfinite(got).all(), (B, N, convention)
+                worst = max(worst, float(np.abs(got - ref).max()))
+    # fp32 exp / sum / divide of at most 8 terms, output in [0, 1]: a few eps (6e-8) each; measured on the MI355X at
+    # most 2.1e-7 (C = 8), 1.2e-7 (C = 2), 0 (C = 1)
+    print("expected_score C=%d: max |err| %.3g (bound 1e-6)" % (C, worst))
+    assert worst < 1e-6
+
+
+def _frames(rng, B, N):
+    """(B, 9, N) row-major frames whose first two columns meet at angles from 1e-2 to pi - 1e-2 rad with magnitudes
+    1e-3 .. 1e3 each (third column arbitrary: the decode ignores it), and the angles (B, N)."""
+    ang = rng.choice([1e-2, 2e-2, 0.1, 0.5, 1.2, np.pi / 2, np.pi - 0.1, np.pi - 1e-2], (B, N))
+    u = rng.standard_normal((B, N, 3))
+    u /= np.linalg.norm(u, axis=-1, keepdims=True)
+    w = rng.standard_normal((B, N, 3))
+    w -= (u * w).sum(-1, keepdims=True) * u
+    w /= np.linalg.norm(w, axis=-1, keepdims=True)
+    c0 = u * 10 ** rng.uniform(-3, 3, (B, N, 1))
+    c1 = (np.cos(ang)[..., None] * u + np.sin(ang)[..., None] * w) * 10 ** rng.uniform(-3, 3, (B, N, 1))
+    c2 = rng.standard_normal((B, N, 3)) * 10 ** rng.uniform(-3, 3, (B, N, 1))
+    R = np.stack([c0, c1, c2], axis=-1)                                          # (B, N, 3, 3), columns c0 c1 c2
+    return np.ascontiguousarray(R.reshape(B, N, 9).transpose(0, 2, 1)).astype(np.float32), ang
+
+
+@pytest.mark.parametrize("K", [1, 63, 64, 65, 200])
+@pytest.mark.parametrize("TC", [1, 2, 3, 4])
+def test_decode_top_poses_edges(dev, K, TC):
+    from s4g_release_amd import postprocess as PP
+    rng = np.random.default_rng(K * 10 + TC)
+    B, N = 2, 300
+    R, ang = _frames(rng, B, N)
+    pred = {"score": rng.standard_normal((B, 3, N)).astype(np.float32) * 2, "frame_R": R,
+            "frame_t": (rng.standard_normal((B, TC, N)) * 4).astype(np.float32)}
+    pts = rng.uniform(-1, 1, (B, 3, N)).astype(np.float32)
+    H, s, sel = PP.decode_top_poses({k: torch.from_numpy(v).to(dev) for k, v in pred.items()},
+                                    torch.from_numpy(pts).to(dev), K)
+    H, s, sel = H.cpu().numpy().astype(np.float64), s.cpu().numpy(), sel.cpu().numpy()
+    assert H.shape == (B, K, 4, 4)
+    # the selection: the K best expected scores, best first
+    es = (torch.softmax(torch.from_numpy(pred["score"]).double(), dim=1).numpy() *
+          np.linspace(0, 1, 4)[:-1][None, :, None]).sum(1)
+    assert np.allclose(s, np.take_along_axis(es, sel, 1), atol=1e-6) and (np.diff(s, axis=1) <= 0).all()
+    assert np.array_equal(np.sort(sel, 1), np.sort(np.argsort(-es, 1)[:, :K], 1))
+    # float64 Gram-Schmidt and translation decode of the selected points' fp32 inputs
+    Rk = np.take_along_axis(R.astype(np.float64), sel[:, None, :], 2).transpose(0, 2, 1).reshape(B, K, 3, 3)
+    c0, c1 = Rk[..., 0], Rk[..., 1]
+    x = c0 / np.linalg.norm(c0, axis=-1, keepdims=True)
+    y = c1 - (x * c1).sum(-1, keepdims=True) * x
+    y /= np.linalg.norm(y, axis=-1, keepdims=True)
+    R64 = np.stack([x, y, np.cross(x, y)], axis=-1)
+    tl = np.take_along_axis(pred["frame_t"].astype(np.float64), sel[:, None, :], 2)
+    tau = (torch.softmax(torch.from_numpy(tl), dim=1).numpy() * np.array(PP.T_BINS[:TC])[None, :, None]).sum(1)
+    p = np.take_along_axis(pts.astype(np.float64), sel[:, None, :], 2).transpose(0, 2, 1)
+    t64 = -tau[..., None] * c0 + p
+    # rotation: the direction of y carries the projection's rounding, ~eps |c1| / (|c1| sin a) -- float32 emulation
+    # of the kernel's arithmetic gives at most 1.9e-7 / sin(a) over angles 1e-2 .. pi/2; measured on the MI355X at
+    # most 1.7e-7 / sin(a) over these cases
+    sin = np.sin(np.take_along_axis(ang, sel, 1))
+    r_err = np.abs(H[..., :3, :3] - R64).max(axis=(-1, -2)) * sin
+    # translation: fp32 softmax of <= 4 bins, one product, one sum: a few eps of |tau c0| + |p|; measured at most
+    # 1.9e-7 of that scale
+    t_err = np.abs(H[..., :3, 3] - t64).max(-1) / (np.abs(tau[..., None] * c0).max(-1) + np.abs(p).max(-1))
+    print("decode K=%d TC=%d: rotation err * sin(a) %.3g (bound 1e-6), translation err / scale %.3g (bound 1e-6)"
+          % (K, TC, r_err.max(), t_err.max()))
+    assert r_err.max() < 1e-6 and t_err.max() < 1e-6
+    # orthonormal even at a = 1e-2: one Gram-Schmidt projection alone leaves x.y ~ eps / sin(a), 3.4e-5 in the float32
+    # emulation -- the kernel projects twice (emulation: at most 5.5e-7 over all angles)
+    RtR = np.einsum("bkij,bkil->bkjl", H[..., :3, :3], H[..., :3, :3])
+    assert np.abs(RtR - np.eye(3)).max() < 1e-5
+    assert np.abs(np.linalg.det(H[..., :3, :3]) - 1).max() < 1e-5                 # right-handed
+    assert (H[..., 3, :] == np.array([0, 0, 0, 1])).all()
