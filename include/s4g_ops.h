@@ -54,8 +54,10 @@ extern "C" {
  * 11: s4g_heads_desc_t.head_mask (a launch may evaluate a subset of the four heads).
  * 12: s4g_test_knobs_enabled (the A/B knobs below are ignored without S4G_TEST_KNOBS=1; no layout change),
  *     s4g_collision_counts_n_f32 (collision counts over padded best-first pose lists with device-side counts),
- *     s4g_sort_pairs_u32 / s4g_exclusive_scan_i32 (the library's own stable radix sort and scan). */
-#define S4G_ABI_VERSION 12
+ *     s4g_sort_pairs_u32 / s4g_exclusive_scan_i32 (the library's own stable radix sort and scan).
+ * 13: s4g_contact_heads_f32 (output tail of the contact network, MODEL.TYPE "PN2"), s4g_decode_poses_abs_f32
+ *     (pose decode for an absolute translation head); no layout change. */
+#define S4G_ABI_VERSION 13
 
 /* ---------------------------------------------------------------------------
  * Environment variables.
@@ -632,6 +634,22 @@ int s4g_decode_poses_f32(const float *xyz_b3n, const float *frame_R_b9n,
                          const float *frame_t_btn, const int64_t *sel_bk, int64_t B,
                          int64_t N, int64_t K, int64_t TC, const float *t_bins,
                          float *H_bk44, s4g_stream_t stream);
+
+/* ABI 13: the contact network (MODEL.TYPE "PN2", reference network_models/models/PointNet2.py).
+ * s4g_contact_heads_f32: raw head logits (B, 17, M) in the order score 3 | R 6 | t 3 | movable 5 (what
+ *   s4g_heads_chain_f32 with out_batch_stride = 17 M, or the channel-first epilogue with the four heads as one
+ *   17-channel head, writes) -> the network's outputs (B, 20, M): score 3 (copied) | frame_R 9 | frame_t 3 |
+ *   movable 5 (copied).  frame_R = toRotMatrix of the 6-D logits (functions/functions.py:179-190: b1 = a1/|a1|,
+ *   b2 = a2 - (a2.b1) b1 normalised, b3 = b1 x b2, channel 3i + j = b_j[i]); frame_t = p + t with p the point's
+ *   coordinates in xyz (B, 3, N): point m, or point index_bm[b, m] (int64, may be NULL when M == N) for a
+ *   forward over a scene's kept points.  Zero or parallel a1 / a2 give NaN in that point's frame_R only.
+ *   raw and out must not overlap.
+ * s4g_decode_poses_abs_f32: like s4g_decode_poses_f32 for an ABSOLUTE translation frame_t (B, 3, N):
+ *   H = [Gram-Schmidt(R) | frame_t[:, sel]] (B, K, 4, 4) row-major. */
+int s4g_contact_heads_f32(const float *raw_b17m, const float *xyz_b3n, const int64_t *index_bm, int64_t B,
+                          int64_t N, int64_t M, float *out_b20m, s4g_stream_t stream);
+int s4g_decode_poses_abs_f32(const float *frame_R_b9n, const float *frame_t_b3n, const int64_t *sel_bk,
+                             int64_t B, int64_t N, int64_t K, float *H_bk44, s4g_stream_t stream);
 
 /* Next row f2: batched gripper-vs-cloud collision counts, replaces the per-pose
  * loop over CloudCollisionChecker.view_non_collision

@@ -13,7 +13,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # declared symbol are checked either way
 LIB_PATH = os.environ.get("S4G_HIP_LIB") or os.path.join(_HERE, "libs4g_hip.so")
 
-S4G_ABI_VERSION = 12
+S4G_ABI_VERSION = 13
 S4G_EINVAL = -1
 S4G_EWORKSPACE = -2
 S4G_EUNSUPPORTED = -3
@@ -106,6 +106,8 @@ SIGNATURES = {
     "s4g_group_rel_xyz_unique_i32": (_int, [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp]),
     "s4g_expected_score_f32": (_int, [_vp, _i64, _i64, _i64, _vp, _vp, _vp]),
     "s4g_decode_poses_f32": (_int, [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _vp, _vp, _vp]),
+    "s4g_contact_heads_f32": (_int, [_vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp]),
+    "s4g_decode_poses_abs_f32": (_int, [_vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp]),
     "s4g_collision_counts_f32": (_int, [_vp, _vp, _i64, _i64, _i64, ctypes.POINTER(ctypes.c_float),
                                         _vp, _vp]),
     "s4g_collision_counts_n_f32": (_int, [_vp, _vp, _i64, _i64, _i64, ctypes.POINTER(ctypes.c_float),

@@ -38,6 +38,28 @@ __global__ __launch_bounds__(256) void expected_score_kernel(
   out[(size_t)b * N + n] = num / den;
 }
 
+// H = [x y z | t; 0 0 0 1] row-major from the row-major 3x3 r (R[i][j] = r[3i + j]): Gram-Schmidt on its first
+// two columns
+__device__ __forceinline__ void gram_schmidt_pose(const float* r, float tx, float ty, float tz, float* __restrict__ h) {
+  float x0 = r[0], x1 = r[3], x2 = r[6];
+  const float xn = sqrtf(x0 * x0 + x1 * x1 + x2 * x2);
+  x0 /= xn; x1 /= xn; x2 /= xn;
+  float y0 = r[1], y1 = r[4], y2 = r[7];
+  const float d = x0 * y0 + x1 * y1 + x2 * y2;
+  y0 -= d * x0; y1 -= d * x1; y2 -= d * x2;
+  // second projection: for nearly parallel columns (angle a) the first leaves x.y ~ eps / sin(a) (3e-5 at a = 1e-2);
+  // repeating it brings x.y back to rounding level
+  const float d2 = x0 * y0 + x1 * y1 + x2 * y2;
+  y0 -= d2 * x0; y1 -= d2 * x1; y2 -= d2 * x2;
+  const float yn = sqrtf(y0 * y0 + y1 * y1 + y2 * y2);
+  y0 /= yn; y1 /= yn; y2 /= yn;
+  const float z0 = x1 * y2 - x2 * y1, z1 = x2 * y0 - x0 * y2, z2 = x0 * y1 - x1 * y0;
+  h[0] = x0; h[1] = y0; h[2] = z0; h[3] = tx;
+  h[4] = x1; h[5] = y1; h[6] = z1; h[7] = ty;
+  h[8] = x2; h[9] = y2; h[10] = z2; h[11] = tz;
+  h[12] = 0.f; h[13] = 0.f; h[14] = 0.f; h[15] = 1.f;
+}
+
 // one thread per selected grasp: 4x4 row-major pose
 __global__ __launch_bounds__(64) void decode_pose_kernel(
     const float* __restrict__ xyz, const float* __restrict__ frame_R,
@@ -63,25 +85,25 @@ __global__ __launch_bounds__(64) void decode_pose_kernel(
   const float tau = num / den;
   const float* p = xyz + (size_t)b * 3 * N + n;
   const float tx = -tau * r[0] + p[0], ty = -tau * r[3] + p[N], tz = -tau * r[6] + p[2 * (size_t)N];
-  // Gram-Schmidt on the first two columns
-  float x0 = r[0], x1 = r[3], x2 = r[6];
-  const float xn = sqrtf(x0 * x0 + x1 * x1 + x2 * x2);
-  x0 /= xn; x1 /= xn; x2 /= xn;
-  float y0 = r[1], y1 = r[4], y2 = r[7];
-  const float d = x0 * y0 + x1 * y1 + x2 * y2;
-  y0 -= d * x0; y1 -= d * x1; y2 -= d * x2;
-  // second projection: for nearly parallel columns (angle a) the first leaves x.y ~ eps / sin(a) (3e-5 at a = 1e-2);
-  // repeating it brings x.y back to rounding level
-  const float d2 = x0 * y0 + x1 * y1 + x2 * y2;
-  y0 -= d2 * x0; y1 -= d2 * x1; y2 -= d2 * x2;
-  const float yn = sqrtf(y0 * y0 + y1 * y1 + y2 * y2);
-  y0 /= yn; y1 /= yn; y2 /= yn;
-  const float z0 = x1 * y2 - x2 * y1, z1 = x2 * y0 - x0 * y2, z2 = x0 * y1 - x1 * y0;
-  float* h = H + ((size_t)b * K + k) * 16;
-  h[0] = x0; h[1] = y0; h[2] = z0; h[3] = tx;
-  h[4] = x1; h[5] = y1; h[6] = z1; h[7] = ty;
-  h[8] = x2; h[9] = y2; h[10] = z2; h[11] = tz;
-  h[12] = 0.f; h[13] = 0.f; h[14] = 0.f; h[15] = 1.f;
+  gram_schmidt_pose(r, tx, ty, tz, H + ((size_t)b * K + k) * 16);
+}
+
+
+// the same for an ABSOLUTE translation (the contact network's frame_t = point + offset, (B, 3, N)): H = [Gram-Schmidt(R)
+// | frame_t[:, sel]], no depth-bin softmax
+__global__ __launch_bounds__(64) void decode_pose_abs_kernel(
+    const float* __restrict__ frame_R, const float* __restrict__ frame_t, const int64_t* __restrict__ sel, int N, int K,
+    float* __restrict__ H) {
+  const int b = blockIdx.y;
+  const int k = blockIdx.x * 64 + threadIdx.x;
+  if (k >= K) return;
+  const int n = (int)sel[(size_t)b * K + k];
+  const float* R = frame_R + (size_t)b * 9 * N + n;     // R[i][j] = channel 3i + j
+  float r[9];
+#pragma unroll
+  for (int c = 0; c < 9; ++c) r[c] = R[(size_t)c * N];
+  const float* t = frame_t + (size_t)b * 3 * N + n;
+  gram_schmidt_pose(r, t[0], t[N], t[2 * (size_t)N], H + ((size_t)b * K + k) * 16);
 }
 
 }  // namespace s4g
@@ -109,6 +131,17 @@ extern "C" int s4g_decode_poses_f32(const float* xyz_b3n, const float* frame_R_b
   hipLaunchKernelGGL(s4g::decode_pose_kernel, dim3((unsigned)((K + 63) / 64), (unsigned)B), dim3(64),
                      0, (hipStream_t)stream, xyz_b3n, frame_R_b9n, frame_t_btn, sel_bk, (int)N,
                      (int)K, (int)TC, t_bins, H_bk44);
+  S4G_LAUNCH_CHECK();
+  return S4G_OK;
+}
+
+extern "C" int s4g_decode_poses_abs_f32(const float* frame_R_b9n, const float* frame_t_b3n, const int64_t* sel_bk,
+                                        int64_t B, int64_t N, int64_t K, float* H_bk44, s4g_stream_t stream) {
+  if (B < 0 || N <= 0 || K < 0 || B > 65535 || N >= (1ll << 31)) return S4G_EINVAL;
+  if (B == 0 || K == 0) return S4G_OK;
+  if (!frame_R_b9n || !frame_t_b3n || !sel_bk || !H_bk44) return S4G_EINVAL;
+  hipLaunchKernelGGL(s4g::decode_pose_abs_kernel, dim3((unsigned)((K + 63) / 64), (unsigned)B), dim3(64), 0,
+                     (hipStream_t)stream, frame_R_b9n, frame_t_b3n, sel_bk, (int)N, (int)K, H_bk44);
   S4G_LAUNCH_CHECK();
   return S4G_OK;
 }

@@ -52,11 +52,16 @@ class Detections(tuple):
 
 
 class GraspDetector:
-    """Device counterpart of the reference class of the same name for `MODEL.TYPE = "PN2_CLS"`."""
+    """Device counterpart of the reference class of the same name, for both networks it names (grasp_detector.py:23,36):
+    `MODEL.TYPE = "PN2_CLS"` (curvature model) and `"PN2"` (contact model).  For the contact model the decode takes
+    the head's absolute grasp position as the translation (`postprocess.detect_poses`); that is this project's
+    definition, not reference parity -- the reference's `post_processing` reads `predictions["score"]` and the 4-bin t
+    decode, so with `contact_model` it raises KeyError."""
 
     def __init__(self, net, precision=None, topk=2048, num_input=25600, camera2base=None,
                  vertical_direction=(0.0, 0.0, 1.0), seed=0, preprocess="shipped", sample_mode="random", gripper=None):
-        """net: a `model.PointNet2` / reference `PointNet2` instance, or a ready `FusedPointNet2`.
+        """net: a `model.PointNet2` / `model.ContactPointNet2` / reference `PointNet2_tcls.PointNet2` /
+        `PointNet2.PointNet2` instance, or a ready `FusedPointNet2` (the kind is read from the logit widths).
         topk: points per scene whose pose heads are evaluated (the K best expected scores).  The result equals the
         full-forward detection whenever fewer than K points of a scene pass the score threshold (always, for a
         threshold of 0.7 on a trained network: the reference then keeps a few hundred).

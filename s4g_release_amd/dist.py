@@ -60,10 +60,20 @@ def shard_range(total, rank, world):
     return lo, lo + base + (1 if rank < extra else 0)
 
 
+def _curvature_only(pred):
+    """The head gather covers the curvature model's four outputs (`HEADS`) only."""
+    if hasattr(pred, "get") and pred.get("scene_score_logits") is not None:
+        raise ValueError("the multi-GPU head gather covers the curvature model (PN2_CLS) only: these are contact-model "
+                         "predictions (scene_score_logits, 20 channels); gather decoded poses instead "
+                         "(OutputGather('poses'))")
+
+
 def pack_outputs(pred):
     """dict of (B, C_h, N) -> one contiguous (B, sum C_h, N) tensor + channel splits.  The fast path's
     `fused.PackedPred` already IS that tensor (the heads launch wrote the four outputs as its channel
-    slices): it is returned as it stands, no copy; any other dict is concatenated."""
+    slices): it is returned as it stands, no copy; any other dict is concatenated.  Contact-model predictions raise
+    ValueError (curvature model only)."""
+    _curvature_only(pred)
     if hasattr(pred, "get") and pred.get("index") is not None:
         # FusedPointNet2(..., topk=K): the (B, 21, K) tensor covers a scene's K kept points only and "index" says which --
         # gathered without it the per-point channels would no longer say which scene points they belong to
@@ -159,6 +169,7 @@ class OutputGather:
         """This rank's contribution as a list of tensors, in the order of `as_list(gathered)`."""
         if self.mode == "poses":
             return list(self.decode(pred, scene_points))
+        _curvature_only(pred)
         return [pred[k] for k in HEADS]
 
     @staticmethod
@@ -170,6 +181,7 @@ class OutputGather:
             H, score, index = self.decode(pred, scene_points)
             self.payload_bytes = H.shape[0] * H.shape[1] * 18 * 4
             return all_gather_poses(H, score, index, self.group)
+        _curvature_only(pred)
         self.payload_bytes = sum(pred[k].numel() * pred[k].element_size() for k in HEADS)
         return all_gather_outputs(pred, self.group)
 

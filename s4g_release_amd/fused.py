@@ -26,6 +26,9 @@ torch's operator set.  What a forward pass launches (round 3, default f16x2 arit
     the logits leave as channel-first rows;
   * FPS also emits the centroid coordinates (no gather launch), ball query and 3-NN emit int32
     indices, 3-NN emits the interpolation weights directly.
+  * the contact network (`MODEL.TYPE: "PN2"`, `model.ContactPointNet2`): the heads write the raw 17 logit channels,
+    then ONE elementwise launch (`s4g_contact_heads_f32`) forms the rotation matrices from the 6-D logits and adds
+    the points to the offsets;
 Twelve contraction launches per forward pass.  `submit()` runs the coordinate-only work (FPS
 pyramid, ball queries, 3-NN) on high-priority geometry streams underneath the previous batch's
 contractions.
@@ -48,6 +51,14 @@ HeadsDesc = _cabi.HeadsDesc
 
 LOAD_PLAIN, LOAD_GATHER, LOAD_INTERP, LOAD_GATHER_MLP1, LOAD_GATHER_ADD, LOAD_INTERP_ADD = 0, 1, 2, 3, 4, 5
 EPI_STORE, EPI_MAX, EPI_CF = 0, 1, 2
+
+# the network kind by the widths of (R_logit, t_logit): the curvature model (PointNet2_tcls.py) or the contact model
+# (PointNet2.py), and the output names of each
+NETWORK_KINDS = {(9, 4): "PN2_CLS", (6, 3): "PN2"}
+HEADS_CLS = ("score", "frame_R", "frame_t", "movable_logits")
+HEADS_CONTACT = ("scene_score_logits", "frame_R", "frame_t", "movable_logits")
+CONTACT_RAW_CHANNELS = (3, 6, 3, 5)      # what s4g_contact_heads_f32 reads ...
+CONTACT_OUT_CHANNELS = (3, 9, 3, 5)      # ... and writes
 
 
 def fold_conv_bn(block):
@@ -158,7 +169,11 @@ class FusedPointNet2:
     """Callable with the reference forward's signature: {"scene_points": (B,3,N)} -> dict."""
 
     def __init__(self, net, precision=None, fold_only=False, check_finite=False):
-        """net: `model.PointNet2` or the reference's own `PointNet2_tcls.PointNet2` instance (the attributes read
+        """net: `model.PointNet2` / `model.ContactPointNet2`, or the reference's own `PointNet2_tcls.PointNet2` /
+        `PointNet2.PointNet2` instance.  The kind is read from the logit widths: R_logit / t_logit 9 / 4 = the
+        curvature model (PN2_CLS, outputs score / frame_R / frame_t / movable_logits as its forward), 6 / 3 = the
+        contact model (PN2: scene_score_logits / frame_R (rotation matrices) / frame_t (points + offsets) /
+        movable_logits, as `PointNet2.py:142-147`); any other pair raises ValueError.  (The attributes read
         are the reference's: `sa_modules[i].{sampler, grouper.{radius, num_neighbours}, mlp, in_channels,
         num_centroids}`, `fp_modules[i].{interpolator._eps, mlp}`, `mlp_seg / seg_logit / mlp_R / R_logit / mlp_t /
         t_logit / mlp_movable / movable_logit[0]`, blocks with `.conv` / `.bn`: `PointNet2_tcls.py:56-95`;
@@ -209,7 +224,9 @@ class FusedPointNet2:
         self.fp_chain_next = _cabi.knob("S4G_FP_CHAIN_NEXT", "1") != "0"
         self.fps_prefix = _cabi.knob("S4G_FPS_PREFIX", "1") != "0"
         # the four head tensors as channel slices of ONE (B, 21, N) tensor (`PackedPred.packed`: the payload of
-        # the multi-GPU all-gather, dist.py, without a packing copy); S4G_PACKED_OUT=0: four tensors of their own
+        # the multi-GPU all-gather, dist.py, without a packing copy); S4G_PACKED_OUT=0: four tensors of their own.
+        # The contact model ignores it: its raw logits are always one (B, 17, N) tensor (the input of the output
+        # tail's launch) and its outputs always slices of one (B, 20, N) tensor
         self.packed_out = _cabi.knob("S4G_PACKED_OUT", "1") != "0"
         p = next(net.parameters())
         self.fold_only = bool(fold_only)
@@ -275,6 +292,15 @@ class FusedPointNet2:
         # heads: order score, R, t, movable (PointNet2_tcls.py:126-140)
         heads = [(net.mlp_seg, net.seg_logit), (net.mlp_R, net.R_logit), (net.mlp_t, net.t_logit),
                  (net.mlp_movable, net.movable_logit[0])]
+        rt = (net.R_logit.weight.shape[0], net.t_logit.weight.shape[0])
+        if rt not in NETWORK_KINDS:
+            raise ValueError("R_logit / t_logit of widths %d / %d: neither the curvature model (9 / 4) nor the contact "
+                             "model (6 / 3)" % rt)
+        self.kind = NETWORK_KINDS[rt]
+        if self.kind == "PN2" and tuple(lg.weight.shape[0] for _, lg in heads) != CONTACT_RAW_CHANNELS:
+            raise ValueError("the contact model's output tail (s4g_contact_heads_f32) takes %s logit channels, not %s"
+                             % (CONTACT_RAW_CHANNELS, tuple(lg.weight.shape[0] for _, lg in heads)))
+        self.out_names = HEADS_CONTACT if self.kind == "PN2" else HEADS_CLS
         depth = len(net.mlp_seg)
         self.head_layers = []
         folded = [[fold_conv_bn(blk) for blk in mlp] for mlp, _ in heads]
@@ -991,9 +1017,28 @@ class FusedPointNet2:
         pred["index"] = sel
         return pred
 
+    def _contact_outputs(self, raw, xyz):
+        """The contact model's outputs from the raw logits of `_dense` (one (B, 17, M) tensor): ONE launch
+        (s4g_contact_heads_f32) writes the (B, 20, M) tensor whose channel slices are scene_score_logits / frame_R /
+        frame_t / movable_logits.  For a top-K forward the kept points' coordinates are read through "index"."""
+        packed = raw.packed
+        B, _, M = packed.shape
+        index = raw.get("index")
+        N = xyz.shape[2]
+        out = torch.empty((B, sum(CONTACT_OUT_CHANNELS), M), dtype=torch.float32, device=packed.device)
+        with _F._timed("contact_heads[M=%d]" % M, B * M * 4 * (sum(CONTACT_RAW_CHANNELS) + sum(CONTACT_OUT_CHANNELS) + 3)):
+            rc = _cabi.lib().s4g_contact_heads_f32(packed.data_ptr(), xyz.data_ptr(),
+                                                   None if index is None else index.data_ptr(), B, N, M,
+                                                   out.data_ptr(), _F._stream())
+        _cabi.check(rc, "contact_heads")
+        pred = PackedPred(zip(HEADS_CONTACT, out.split(CONTACT_OUT_CHANNELS, dim=1)), packed=out)
+        if index is not None:
+            pred["index"] = index
+        return pred
+
     def _head_outputs(self, B, N0, dev):
         """(packed (B, sum c_h, N) tensor or None, the four (B, c_h, N) head tensors -- its channel slices)."""
-        if not self.packed_out:
+        if not self.packed_out and self.kind != "PN2":
             return None, [torch.empty((B, c, N0), dtype=torch.float32, device=dev) for c in self.head_channels]
         packed = torch.empty((B, sum(self.head_channels), N0), dtype=torch.float32, device=dev)
         return packed, list(packed.split(self.head_channels, dim=1))
@@ -1042,6 +1087,8 @@ class FusedPointNet2:
             ds.wait_event(ev_in)
             with torch.cuda.stream(ds):
                 pred = self._dense(xyz, geo, topk=topk)
+                if self.kind == "PN2":
+                    pred = self._contact_outputs(pred, xyz)
                 ev_out = ds.record_event()
             # tensors cross streams: tell the caching allocator
             xyz.record_stream(gs)
@@ -1085,7 +1132,9 @@ class PackedPred(dict):
     """The forward's output dict (`PointNet2_tcls.py:142-147`: score / frame_R / frame_t / movable_logits).  On the
     fast path the four tensors are channel slices of `packed`, ONE (B, 21, N) tensor in the head order of
     `dist.HEADS` that the heads launch wrote directly -- `dist.pack_outputs` hands it to the all-gather as it
-    is.  `packed` is None when the tensors are separate allocations (S4G_PACKED_OUT=0)."""
+    is.  `packed` is None when the tensors are separate allocations (S4G_PACKED_OUT=0).  The contact model's
+    (`PointNet2.py:142-147`: scene_score_logits / frame_R / frame_t / movable_logits) are slices of one (B, 20, N)
+    tensor."""
 
     def __init__(self, items=(), packed=None):
         super().__init__(items)

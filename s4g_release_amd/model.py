@@ -1,5 +1,6 @@
-"""The S4G network (`MODEL.TYPE: "PN2_CLS"`): 3 set-abstraction layers, 3
-feature-propagation layers and four per-point heads.
+"""The S4G networks: `MODEL.TYPE: "PN2_CLS"` (the curvature model, `PointNet2`) and `MODEL.TYPE: "PN2"` (the
+contact model, `ContactPointNet2`) -- 3 set-abstraction layers, 3 feature-propagation layers and four per-point
+heads; the two differ only after the last logit layer of the rotation and translation heads.
 
 Mirror of reference `network_models/models/PointNet2_tcls.py:10-153` (class
 `PointNet2`) with the hyper-parameters of
@@ -9,6 +10,10 @@ entries, so `load_checkpoint` accepts a real
 `curvature_model.pth` (`{"model": state_dict}`, optional `module.` prefixes --
 reference `utils/checkpoint.py:31,54-55,81-88`).  Loss / metric classes are
 training-only and out of scope.
+
+`ContactPointNet2` mirrors reference `network_models/models/PointNet2.py` (class `PointNet2`, config
+`configs/contact_model.yaml`, whose hyper-parameters equal the curvature model's): 6-D rotation logits turned into
+a rotation matrix by `to_rot_matrix` (`functions/functions.py:179-190`) and a 3-D offset added to the point.
 """
 from dataclasses import dataclass, field
 from typing import Tuple
@@ -54,6 +59,7 @@ class PointNet2(nn.Module):
     """
     _SA_MODULE = PointNetSAModule
     _FP_MODULE = PointnetFPModule
+    _R_CHANNELS, _T_CHANNELS = 9, 4          # rotation / translation logit widths
 
     def __init__(self, score_classes, num_centroids=(10240, 1024, 128, 0),
                  radius=(0.2, 0.3, 0.4, -1.0), num_neighbours=(64, 64, 64, -1),
@@ -87,9 +93,9 @@ class PointNet2(nn.Module):
         self.mlp_seg = SharedMLP(c, seg_channels, ndim=1, dropout_prob=dropout_prob)
         self.seg_logit = nn.Conv1d(seg_channels[-1], score_classes, 1, bias=True)
         self.mlp_R = SharedMLP(c, seg_channels, ndim=1)
-        self.R_logit = nn.Conv1d(seg_channels[-1], 9, 1, bias=True)
+        self.R_logit = nn.Conv1d(seg_channels[-1], self._R_CHANNELS, 1, bias=True)
         self.mlp_t = SharedMLP(c, seg_channels, ndim=1)
-        self.t_logit = nn.Conv1d(seg_channels[-1], 4, 1, bias=True)
+        self.t_logit = nn.Conv1d(seg_channels[-1], self._T_CHANNELS, 1, bias=True)
         self.mlp_movable = SharedMLP(c, seg_channels, ndim=1, dropout_prob=dropout_prob)
         self.movable_logit = nn.Sequential(
             nn.Conv1d(seg_channels[-1], num_removal_directions, 1, bias=True), nn.Sigmoid())
@@ -112,6 +118,58 @@ class PointNet2(nn.Module):
                 "frame_R": self.R_logit(self.mlp_R(x)),
                 "frame_t": self.t_logit(self.mlp_t(x)),
                 "movable_logits": self.movable_logit(self.mlp_movable(x))}
+
+
+def to_rot_matrix(repre6d):
+    """`toRotMatrix` (reference functions/functions.py:179-190): (B, 6, N) -> (B, 9, N) with channel 3i + j = b_j[i],
+    b1 = a1 / |a1|, b2 = a2 - (a2 . b1) b1 normalised, b3 = b1 x b2.  Differentiable (torch ops)."""
+    b1 = repre6d[:, :3, :].contiguous()
+    b1 = b1 / torch.norm(b1, dim=1, keepdim=True)
+    a2 = repre6d[:, 3:6, :].contiguous()
+    b2 = a2 - (torch.sum(a2 * b1, dim=1, keepdim=True) * b1)
+    b2 = b2 / torch.norm(b2, dim=1, keepdim=True)
+    b3 = torch.cross(b1, b2, dim=1)
+    R = torch.stack([b1, b2, b3], dim=2)
+    return R.contiguous().view(R.shape[0], 9, -1)
+
+
+class ContactPointNet2(PointNet2):
+    """The contact network (`MODEL.TYPE: "PN2"`, reference network_models/models/PointNet2.py:10-152): the same
+    modules as `PointNet2` except `R_logit` (6 outputs, the 6-D rotation representation) and `t_logit` (3 outputs,
+    an offset from the point; zero-initialised, :149-152).  The state_dict has the same 200 entries.
+
+    forward({"scene_points": (B,3,N) f32}) ->
+      {"scene_score_logits": (B,score_classes,N), "frame_R": (B,9,N) rotation matrices (channel 3i + j = R[i][j]),
+       "frame_t": (B,3,N) = scene_points + offset, "movable_logits": (B,num_removal_directions,N) (after Sigmoid)}
+    """
+
+    _R_CHANNELS, _T_CHANNELS = 6, 3
+
+    def __init__(self, *args, **kwargs):
+        super().__init__(*args, **kwargs)
+        nn.init.zeros_(self.t_logit.weight)
+        nn.init.zeros_(self.t_logit.bias)
+
+    def forward(self, data_batch):
+        points = data_batch["scene_points"]
+        pred = super().forward(data_batch)
+        return {"scene_score_logits": pred["score"],
+                "frame_R": to_rot_matrix(pred["frame_R"]),
+                "frame_t": points + pred["frame_t"],
+                "movable_logits": pred["movable_logits"]}
+
+
+MODEL_TYPES = {"PN2_CLS": PointNet2, "PN2": ContactPointNet2}
+
+
+def build_model(model_type, cfg=None):
+    """The network of a `MODEL.TYPE` (reference grasp_detector.py:23,36): "PN2_CLS" -> `PointNet2` (curvature
+    model), "PN2" -> `ContactPointNet2` (contact model); `cfg` an `S4GConfig` (default: the shipped values, which
+    both configs share).  Any other type raises ValueError."""
+    if model_type not in MODEL_TYPES:
+        raise ValueError("unsupported MODEL.TYPE %r: expected one of %s" % (model_type, sorted(MODEL_TYPES)))
+    cfg = cfg or S4GConfig()
+    return MODEL_TYPES[model_type](**cfg.model_kwargs())
 
 
 def build_pointnet2_cls(cfg=None):

@@ -5,6 +5,13 @@ reference's callers (`grasp_proposal_test.py:83` -> `utils/file_logger_cls.py`,
 `decode_top_poses` turns the four head tensors into the K best grasp frames per
 scene entirely on the GPU, so a serving loop ships K x 18 floats per scene
 instead of 21 x N.  Collision filtering (row f2) is not part of it.
+
+Both networks decode here.  The curvature model (PN2_CLS: "score", frame_t = 4 depth-bin logits) as the reference's
+callers do.  The contact model (PN2: "scene_score_logits", frame_t = the absolute grasp position (B, 3, N)) with this
+project's definition: the same expected score, thresholds, order and Gram-Schmidt, and the head's absolute position
+as the translation (`s4g_decode_poses_abs_f32`).  That is not a parity claim: the reference's own decode
+(`GraspDetector.post_processing`, `file_logger_cls.py`) reads `predictions["score"]` and the 4-bin t decode, so with
+`contact_model` it raises KeyError.
 """
 import ctypes
 import math
@@ -84,6 +91,39 @@ def expected_score(score_logits, convention="demo"):
     return out
 
 
+def _is_contact(predictions):
+    """True for the contact model's predictions ("scene_score_logits", frame_t (B, 3, N) absolute positions)."""
+    if "scene_score_logits" not in predictions:
+        return False
+    if predictions["frame_t"].shape[1] != 3:
+        raise ValueError("contact-model predictions need frame_t of 3 channels (absolute positions), got %d"
+                         % predictions["frame_t"].shape[1])
+    return True
+
+
+def _score_logits(predictions):
+    return predictions["scene_score_logits"] if _is_contact(predictions) else predictions["score"]
+
+
+def _decode(xyz, R, t, sel, contact):
+    """(B, K, 4, 4) row-major poses of the points sel (B, K): `s4g_decode_poses_abs_f32` for an absolute frame_t
+    (contact model), `s4g_decode_poses_f32` with the depth bins otherwise."""
+    B, _, N = R.shape
+    K = sel.shape[1]
+    H = torch.empty((B, K, 4, 4), dtype=torch.float32, device=R.device)
+    with torch.cuda.device(R.device):
+        if contact:
+            rc = _cabi.lib().s4g_decode_poses_abs_f32(R.data_ptr(), t.data_ptr(), sel.data_ptr(), B, N, K,
+                                                      H.data_ptr(), _F._stream())
+        else:
+            bins = _dev_const(("t_bins", t.shape[1]), lambda: torch.tensor(T_BINS[:t.shape[1]], dtype=torch.float32),
+                              R.device)
+            rc = _cabi.lib().s4g_decode_poses_f32(xyz.data_ptr(), R.data_ptr(), t.data_ptr(), sel.data_ptr(), B, N,
+                                                  K, t.shape[1], bins.data_ptr(), H.data_ptr(), _F._stream())
+    _cabi.check(rc, "decode_poses")
+    return H
+
+
 def _kept_points(predictions, scene_points):
     """Predictions of `FusedPointNet2(..., topk=K)` cover a scene's K best-scoring points only and carry their point
     numbers in "index": (those points' coordinates (B, 3, K), index) -- or (scene_points, None) for a full forward."""
@@ -96,7 +136,8 @@ def _kept_points(predictions, scene_points):
 def decode_top_poses(predictions, scene_points, num_poses=50, convention="demo"):
     """-> (H (B,K,4,4) fp32, score (B,K) fp32, index (B,K) int64), best first
     (file_logger_cls.py:196-218: K = 50, argsort(-score)[:K], Gram-Schmidt).  Predictions over a scene's kept points
-    (`FusedPointNet2(..., topk=)`) are accepted too: the returned index numbers the scene's points either way."""
+    (`FusedPointNet2(..., topk=)`) are accepted too: the returned index numbers the scene's points either way.
+    Contact-model predictions take frame_t as the translation (module docstring)."""
     scene_points, kept = _kept_points(predictions, scene_points)
     if kept is not None:
         H, top, sel = decode_top_poses({k: v for k, v in predictions.items() if k != "index"}, scene_points,
@@ -105,19 +146,12 @@ def decode_top_poses(predictions, scene_points, num_poses=50, convention="demo")
     xyz = _F._f32c(scene_points, "scene_points")
     R = _F._f32c(predictions["frame_R"], "frame_R")
     t = _F._f32c(predictions["frame_t"], "frame_t")
-    score = expected_score(predictions["score"], convention)
+    score = expected_score(_score_logits(predictions), convention)
     B, _, N = xyz.shape
     K = min(int(num_poses), N)
     top, sel = torch.topk(score, K, dim=1, largest=True, sorted=True)
     sel = sel.contiguous()
-    bins = _dev_const(("t_bins", t.shape[1]), lambda: torch.tensor(T_BINS[:t.shape[1]], dtype=torch.float32), xyz.device)
-    H = torch.empty((B, K, 4, 4), dtype=torch.float32, device=xyz.device)
-    with torch.cuda.device(xyz.device):
-        rc = _cabi.lib().s4g_decode_poses_f32(xyz.data_ptr(), R.data_ptr(), t.data_ptr(),
-                                              sel.data_ptr(), B, N, K, t.shape[1], bins.data_ptr(),
-                                              H.data_ptr(), _F._stream())
-    _cabi.check(rc, "decode_poses")
-    return H, top, sel
+    return _decode(xyz, R, t, sel, _is_contact(predictions)), top, sel
 
 
 REAL2TRAIN = ((0., 1., 0., 0.), (1., 0., 0., 0.), (0., 0., -1., 0.), (0., 0., 0., 1.))   # grasp_detector.py:26
@@ -204,7 +238,17 @@ def detect_poses(predictions, scene_points, score_threshold=0.7, verticalness_th
     what the reference's comments describe.  `reference_indexing=True` reproduces what its lines
     :149-167 actually compute (a position list used as point indices and a numpy transpose that is
     a no-op; see `_detect_poses_as_written`): same poses, scores and order as the reference, pinned
-    by tests/golden/post_detector.npz which the reference's own function generated."""
+    by tests/golden/post_detector.npz which the reference's own function generated.
+
+    Contact-model predictions ("scene_score_logits", frame_t (B, 3, N) absolute grasp positions) take the same
+    expected score, thresholds, order, verticalness on R[:, :, 0] and `frame @ H`, with the head's absolute position
+    as the translation (`s4g_decode_poses_abs_f32`).  This is this project's definition, not a reference parity
+    claim: the reference's own `post_processing` reads `predictions["score"]` and decodes t from 4 depth bins, so
+    with `contact_model` it raises KeyError.  `reference_indexing=True` raises ValueError for them."""
+    contact = _is_contact(predictions)
+    if contact and reference_indexing:
+        raise ValueError("reference_indexing=True restates the reference's curvature-model post_processing: it does not "
+                         "apply to contact-model predictions")
     scene_points, kept = _kept_points(predictions, scene_points)
     if kept is not None:
         # (exact whenever the kept points contain every candidate the filters would pass among the best max_poses:
@@ -221,7 +265,7 @@ def detect_poses(predictions, scene_points, score_threshold=0.7, verticalness_th
     xyz = _F._f32c(scene_points, "scene_points")
     R = _F._f32c(predictions["frame_R"], "frame_R")
     t = _F._f32c(predictions["frame_t"], "frame_t")
-    score = expected_score(predictions["score"], "detector")                    # (B, N)
+    score = expected_score(_score_logits(predictions), "detector")              # (B, N)
     B, _, N = xyz.shape
     dev = xyz.device
     dm = _small_on_device(((1., 0., 0.), (0., 1., 0.), (0., 0., 1.)) if direction_matrix is None else direction_matrix,
@@ -236,13 +280,7 @@ def detect_poses(predictions, scene_points, score_threshold=0.7, verticalness_th
     top, sel = torch.sort(key, dim=1, descending=True, stable=True)
     top, sel = top[:, :K], sel[:, :K].contiguous()
     count = keep.sum(dim=1).clamp(max=K)
-    bins = _dev_const(("t_bins", t.shape[1]), lambda: torch.tensor(T_BINS[:t.shape[1]], dtype=torch.float32), dev)
-    H = torch.empty((B, K, 4, 4), dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        rc = _cabi.lib().s4g_decode_poses_f32(xyz.data_ptr(), R.data_ptr(), t.data_ptr(),
-                                              sel.data_ptr(), B, N, K, t.shape[1], bins.data_ptr(),
-                                              H.data_ptr(), _F._stream())
-    _cabi.check(rc, "decode_poses")
+    H = _decode(xyz, R, t, sel, contact)
     fr = _small_on_device(frame, torch.float32, dev)
     # frame @ H for every pose: a broadcast multiply + sum over the 4-long contraction (one elementwise kernel + one
     # reduction) -- `torch.matmul` dispatches 32 768 4x4 products to a batched library GEMM: 0.52 ms per call in the
