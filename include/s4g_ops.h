@@ -56,8 +56,10 @@ extern "C" {
  *     s4g_collision_counts_n_f32 (collision counts over padded best-first pose lists with device-side counts),
  *     s4g_sort_pairs_u32 / s4g_exclusive_scan_i32 (the library's own stable radix sort and scan).
  * 13: s4g_contact_heads_f32 (output tail of the contact network, MODEL.TYPE "PN2"), s4g_decode_poses_abs_f32
- *     (pose decode for an absolute translation head); no layout change. */
-#define S4G_ABI_VERSION 13
+ *     (pose decode for an absolute translation head); no layout change.
+ * 14: S4G_GEMM_LOAD_CHANNEL_FIRST, S4G_GEMM_EPI_MAX_CHANNEL_FIRST and s4g_gemm_desc_t.a_L (any SharedMLP / SA max-pool
+ *     on its own (B, C, L) tensors: s4g_release_amd.accelerate), s4g_amax_per_scene_f32. */
+#define S4G_ABI_VERSION 14
 
 /* ---------------------------------------------------------------------------
  * Environment variables.
@@ -284,6 +286,11 @@ int s4g_interp_weights_f32(const float *d2_bn3, int64_t B, int64_t N1,
  *                                A row p = relu(F[b*N + gidx[p]] + W_xyz . (xyz - ctr) + b1),
  *                                mlp1_w = Cin x (wx, wy, wz, bias); a_amax bounds |F| and
  *                                a_amax_floor the xyz + bias part (the two are ADDED)
+ *         S4G_GEMM_LOAD_CHANNEL_FIRST  (ABI >= 14) A is a (B, Cin, a_L) fp32 tensor, channels first:
+ *                                A row p = b*a_L + l = A[b][0..Cin)[l]; any Cin >= 1 and any a_L >= 1
+ *                                (P % a_L == 0), columns past Cin read as zero.  Lanes walk positions,
+ *                                so a wave reads contiguous runs of one channel; the transpose to
+ *                                [position][channel] happens on the way into LDS.  FP32 / F16X2 only
  *         S4G_GEMM_LOAD_INTERP_ADD  first FP layer applied before the interpolation (linear):
  *                                A row p = relu(dense[p] + loader_bias + sum_k nw[p,k] *
  *                                sparse[b*N2 + nidx[p,k]]), sparse = W_a . sparse features and
@@ -295,6 +302,14 @@ int s4g_interp_weights_f32(const float *d2_bn3, int64_t B, int64_t N1,
  *          S4G_GEMM_EPI_CHANNEL_FIRST  (B,C,N) tensors cf_ptr[h], channel
  *                               ranges cf_start[h]..cf_start[h+1], sigmoid on
  *                               channels >= cf_sigmoid_from
+ *          S4G_GEMM_EPI_MAX_CHANNEL_FIRST  (ABI >= 14) out (B, Cout, M) channels first:
+ *                               out[b][n][m] = relu(bias[n] + max over the K consecutive rows of
+ *                               group b*M + m), any K >= 1 and M >= 1 (P % (M*K) == 0; groups may
+ *                               straddle row tiles).  relu must be 1 (else S4G_EINVAL); `out` must be
+ *                               zero-filled by the caller: a tile reduces its rows first and merges
+ *                               each (group, channel) it holds with ONE unsigned atomicMax on the bits
+ *                               of the non-negative result (order-independent: deterministic).
+ *                               FP32 / F16X2 only
  * W is [groups][Cout][Kpad] with Kpad % 8 == 0 (zero padded), bias
  * [groups][Cout].  Cf, C2, lda, a_coff, C1 must be multiples of 4.
  * ------------------------------------------------------------------------- */
@@ -304,9 +319,11 @@ int s4g_interp_weights_f32(const float *d2_bn3, int64_t B, int64_t N1,
 #define S4G_GEMM_LOAD_GATHER_MLP1 3
 #define S4G_GEMM_LOAD_GATHER_ADD 4
 #define S4G_GEMM_LOAD_INTERP_ADD 5
+#define S4G_GEMM_LOAD_CHANNEL_FIRST 6
 #define S4G_GEMM_EPI_STORE 0
 #define S4G_GEMM_EPI_MAX 1
 #define S4G_GEMM_EPI_CHANNEL_FIRST 2
+#define S4G_GEMM_EPI_MAX_CHANNEL_FIRST 3
 #define S4G_GEMM_FP32 0
 #define S4G_GEMM_BF16X3 1
 #define S4G_GEMM_BF16 2 /* reduced precision: one bf16 product, fp32 accumulate */
@@ -430,6 +447,9 @@ typedef struct s4g_gemm_desc {
   float *out2;
   int32_t ldc2, split_n;
   float *out_amax2;
+  /* ABI >= 14: S4G_GEMM_LOAD_CHANNEL_FIRST: positions per scene of the (B, Cin, a_L) input (N of a (B, C, N)
+   * tensor, M*K of a (B, C, M, K) one).  rows_per_scene = a_L gives per-scene scales. */
+  int32_t a_L;
 } s4g_gemm_desc_t;
 
 int s4g_mlp_gemm_f32(const s4g_gemm_desc_t *desc, s4g_stream_t stream);
@@ -494,6 +514,11 @@ typedef struct s4g_heads_desc {
 } s4g_heads_desc_t;
 
 int s4g_heads_chain_f32(const s4g_heads_desc_t *desc, s4g_stream_t stream);
+
+/* ABI >= 14.  Per-scene bound of |x| for f16x2 inputs that no launch of this library produced: x is B scenes of
+ * n_per_scene fp32 values each; slot row b of out_slots ((B, 64) uint32, ZEROED by the caller) receives atomicMax
+ * of the bits of max |x| over scene b -- the layout s4g_gemm_desc_t.a_amax reads with rows_per_scene > 0. */
+int s4g_amax_per_scene_f32(const float *x, int64_t B, int64_t n_per_scene, float *out_slots, s4g_stream_t stream);
 
 /* 1 when s4g_mlp_gemm_f32 has a fused-chain form (W2_f16x2_frag set) for this first-layer
  * loader, final epilogue, chain width C (= Cout = Cout2 of a three-layer chain) and first-layer

@@ -7,3 +7,10 @@ Importing the package does not touch the GPU and does not load the HIP library;
 the first operator call does, and fails loudly if ``libs4g_hip.so`` is absent.
 """
 __version__ = "0.1.0"
+
+
+def accelerate(net, precision="f16x2"):
+    """Run every SharedMLP and SA max-pool of `net` (any PointNet++ graph, the reference's own instances included) on
+    the HIP contraction kernels; returns the qualified names of the converted modules.  See `accelerated.py`."""
+    from .accelerated import accelerate as _accelerate
+    return _accelerate(net, precision)

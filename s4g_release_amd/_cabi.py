@@ -13,7 +13,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # declared symbol are checked either way
 LIB_PATH = os.environ.get("S4G_HIP_LIB") or os.path.join(_HERE, "libs4g_hip.so")
 
-S4G_ABI_VERSION = 13
+S4G_ABI_VERSION = 14
 S4G_EINVAL = -1
 S4G_EWORKSPACE = -2
 S4G_EUNSUPPORTED = -3
@@ -49,6 +49,7 @@ class GemmDesc(ctypes.Structure):
         ("W3_f16x2_frag", _vp), ("w3_inv_scale", _vp), ("bias3", _vp), ("Cout3", _i32), ("relu3", _i32),
         ("loader_bias", _vp), ("rows_per_scene", _i32), ("rel_xyz4", _vp), ("seg4", _vp), ("seg_rows", _vp),
         ("out2", _vp), ("ldc2", _i32), ("split_n", _i32), ("out_amax2", _vp),
+        ("a_L", _i32),
     ]
 
 
@@ -81,6 +82,7 @@ SIGNATURES = {
     "s4g_three_nn_grid_f32": (_int, [_vp, _vp, _i64, _i64, _i64, _f32, _vp, _vp, _vp, _sz, _int, _vp]),
     "s4g_group_points_xyz_f32": (_int, [_vp, _vp, _i64, _i64, _i64, _i64, _vp, _vp, _sz, _vp]),
     "s4g_gemm_chain_supported": (_int, [_int, _int, _int, _int]),
+    "s4g_amax_per_scene_f32": (_int, [_vp, _i64, _i64, _vp, _vp]),
     "s4g_interp_add_cl_f32": (_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _int, _vp, _vp, _vp]),
     "s4g_group_points_ws_f32": (_int, [_vp, _vp, _i64, _i64, _i64, _i64, _i64, _vp, _vp, _sz, _vp]),
     "s4g_three_interpolate_ws_f32": (_int, [_vp, _vp, _vp, _i64, _i64, _i64, _i64, _vp, _vp, _sz, _int, _vp]),

@@ -65,20 +65,21 @@ constexpr int GM_LDS = 36;  // padded row stride (floats)
 constexpr int GM_THREADS = 256;
 
 enum { LOAD_PLAIN = 0, LOAD_GATHER = 1, LOAD_INTERP = 2, LOAD_GATHER_MLP1 = 3, LOAD_GATHER_ADD = 4,
-       LOAD_INTERP_ADD = 5,
+       LOAD_INTERP_ADD = 5, LOAD_CHANNEL_FIRST = 6,
        // internal (never in a descriptor): GATHER_MLP1 on pre-gathered rel_xyz4 records in the f16x2 chain kernel --
        // the 3 -> C first layer runs on the matrix cores too (mlp_chain_kernel, "phase 0")
-       LOAD_REL_MLP1 = 6 };
-enum { EPI_STORE = 0, EPI_MAX = 1, EPI_CHANNEL_FIRST = 2 };
+       LOAD_REL_MLP1 = 64 };
+enum { EPI_STORE = 0, EPI_MAX = 1, EPI_CHANNEL_FIRST = 2, EPI_MAX_CF = 3 };
 
 struct GemmParams {
   // problem
   int P, Cin, Kpad, Cout, relu;
   const float* W;     // [groups][Cout][Kpad]
   const float* bias;  // [groups][Cout]
-  // PLAIN: A + p*lda + a_coff + g*a_gcol
+  // PLAIN: A + p*lda + a_coff + g*a_gcol; CHANNEL_FIRST: A (B, Cin, aL), row p = b*aL + l
   const float* A;
   int lda, a_coff, a_gcol;
+  int aL;
   // GATHER: feat (B*N, Cf) channels-last, xyz (B,3,N), ctr (B,3,M), idx (B*M*K) int32
   const int* gidx;
   const float* feat;
@@ -164,7 +165,12 @@ __device__ __forceinline__ void gather_row_bm(int M, int K, int p0, int r, int& 
 
 template <int LOADER, int RPT = 4, int RS = 32>
 struct ALoader {
-  // per-thread: RPT rows (t>>3)+RS*s, one 4-float chunk (t&7)
+  // per-thread: RPT rows srow(t)+RS*s, one 4-float chunk chunk(t).  Row-major sources: row t>>3, chunk t&7 --
+  // eight lanes read one row's 128 bytes.  CHANNEL_FIRST (A[b][k][l]): a wave's lanes walk 32 consecutive
+  // positions of one chunk, so each of its four channel loads is a contiguous 128-byte run; the thread's
+  // 4 channels of one row leave as one chunk (the transpose happens on the way into LDS)
+  static __device__ __forceinline__ int srow(int t) { return LOADER == LOAD_CHANNEL_FIRST ? (t & 31) : (t >> 3); }
+  static __device__ __forceinline__ int chunk(int t) { return LOADER == LOAD_CHANNEL_FIRST ? (t >> 5) : (t & 7); }
   const float* src0[RPT];  // PLAIN: row base; GATHER: feat row base; INTERP: unused
   bool ok[RPT];
   // GATHER tail
@@ -183,7 +189,7 @@ struct ALoader {
     int pp_[RPT], j_[RPT], b_[RPT], m_[RPT];
 #pragma unroll
     for (int s = 0; s < RPT; ++s) {
-      const int r = (t >> 3) + RS * s;
+      const int r = srow(t) + RS * s;
       const int pos = p0 + r;
       ok[s] = pos < p.P;
       pp_[s] = ok[s] ? pos : 0;
@@ -200,6 +206,9 @@ struct ALoader {
       const int pp = pp_[s], j = j_[s], b = b_[s], m = m_[s];
       if constexpr (LOADER == LOAD_PLAIN) {
         src0[s] = p.A + (size_t)pp * p.lda + p.a_coff + g * p.a_gcol;
+      } else if constexpr (LOADER == LOAD_CHANNEL_FIRST) {
+        const int b = pp / p.aL;
+        src0[s] = p.A + (size_t)b * p.Cin * p.aL + (pp - b * p.aL);   // channel 0 of the row
       } else if constexpr (LOADER == LOAD_GATHER_MLP1) {
         if (p.rel4) {   // pre-gathered by s4g_group_rel_xyz_i32: one coalesced 16-byte read per row
           const float4 r4 = p.rel4[pp];
@@ -281,6 +290,11 @@ struct ALoader {
     if constexpr (LOADER == LOAD_PLAIN) {
       if (k0 >= p.Cin) return f4zero();
       return *reinterpret_cast<const float4*>(src0[s] + k0);
+    } else if constexpr (LOADER == LOAD_CHANNEL_FIRST) {
+      float v[4];
+#pragma unroll
+      for (int e = 0; e < 4; ++e) v[e] = k0 + e < p.Cin ? src0[s][(size_t)(k0 + e) * p.aL] : 0.f;
+      return make_float4(v[0], v[1], v[2], v[3]);
     } else if constexpr (LOADER == LOAD_INTERP_ADD) {
       // first FP layer applied before the interpolation: A = relu(y + bias + sum_k w_k S[idx_k])
       if (k0 >= p.Cin) return f4zero();
@@ -479,6 +493,60 @@ __device__ __forceinline__ void gemm_epilogue(const GemmParams& p, f32x16 (&acc)
   }
 }
 
+// EPI_MAX_CF: out[b][n][m] = relu(bias[n] + max over the K consecutive rows of group g = b*M + m), any K,
+// channels-first output.  The tile is staged through LDS 32 rows at a time (slice j = rows 32 j .. 32 j + 31,
+// held by the waves of row half j / 2 in accumulator block j % 2); thread c < BN owns column c and walks the
+// tile's 128 rows in order with a running maximum of the current group.  Each (tile, group, column) leaves with
+// ONE unsigned atomicMax on the bits of its non-negative post-ReLU value (out zero-filled by the caller), so a
+// group that straddles tiles is merged order-independently; zero results are not sent at all.
+template <int NCB>
+__device__ __forceinline__ void max_cf_epilogue(const GemmParams& p, f32x16 (&acc)[2][NCB],
+                                                const float* __restrict__ bg, int p0, int n0, int wr, int wc,
+                                                int li, int lh, float* __restrict__ stage) {
+  constexpr int BN = 64 * NCB;
+  constexpr int SS = BN + 1;   // odd row stride: the column walk reads 64 consecutive banks
+  const int t = threadIdx.x;
+  const int n = n0 + t;
+  const bool own = t < BN && n < p.Cout;
+  const float bias = own ? bg[n] : 0.f;
+  int grp = p0 / p.K;
+  int rem = p0 - grp * p.K;
+  float run = -__builtin_inff();
+  auto flush = [&]() {
+    const float v = run + bias;
+    if (v > 0.f) {   // (also keeps -0.0 out of the unsigned ordering)
+      const int b = grp / p.M;
+      const int m = grp - b * p.M;
+      atomicMax(reinterpret_cast<unsigned int*>(p.out) + ((size_t)b * p.Cout + n) * p.M + m, __float_as_uint(v));
+    }
+  };
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    if (wr == (j >> 1)) {
+#pragma unroll
+      for (int cb = 0; cb < NCB; ++cb)
+#pragma unroll
+        for (int r = 0; r < 16; ++r)
+          stage[((r & 3) + 8 * (r >> 2) + 4 * lh) * SS + wc * 32 * NCB + cb * 32 + li] = acc[j & 1][cb][r];
+    }
+    __syncthreads();
+    if (own) {
+      const int rows = min(32, p.P - (p0 + 32 * j));
+      for (int i = 0; i < rows; ++i) {
+        run = fmaxf(run, stage[i * SS + t]);
+        if (++rem == p.K) {
+          flush();
+          run = -__builtin_inff();
+          rem = 0;
+          ++grp;
+        }
+      }
+    }
+    __syncthreads();
+  }
+  if (own && rem > 0) flush();   // the group goes on in the next tile
+}
+
 template <int LOADER, int EPI>
 __global__ __launch_bounds__(GM_THREADS, 2) void mlp_gemm_kernel(const GemmParams p) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -510,6 +578,8 @@ __global__ __launch_bounds__(GM_THREADS, 2) void mlp_gemm_kernel(const GemmParam
   ld.init(p, p0, g, t);
   const int chunk = t & 7;
   const int srow = t >> 3;
+  const int achunk = ALoader<LOADER>::chunk(t);
+  const int a_st_off = ALoader<LOADER>::srow(t) * GM_LDS + achunk * 4;
   const float* wrow[4];
   bool wok[4];
 #pragma unroll
@@ -538,15 +608,16 @@ __global__ __launch_bounds__(GM_THREADS, 2) void mlp_gemm_kernel(const GemmParam
 
   auto gload = [&](int kt) {
     const int k0 = kt * GM_BK + chunk * 4;
+    const int ka = kt * GM_BK + achunk * 4;
     const bool live = k0 < p.Kpad;
 #pragma unroll
     for (int s = 0; s < 4; ++s) {
-      ra[s] = live ? ld.load(p, s, k0, t) : f4zero();
+      ra[s] = ka < p.Kpad ? ld.load(p, s, ka, t) : f4zero();
       rw[s] = (live && wok[s]) ? *reinterpret_cast<const float4*>(wrow[s] + k0) : f4zero();
     }
   };
   auto lstore = [&](int buf) {
-    float* a = As + buf * GM_BM * GM_LDS + st_off;
+    float* a = As + buf * GM_BM * GM_LDS + a_st_off;
     float* w = Ws + buf * GM_BN * GM_LDS + st_off;
 #pragma unroll
     for (int s = 0; s < 4; ++s) {
@@ -585,7 +656,10 @@ __global__ __launch_bounds__(GM_THREADS, 2) void mlp_gemm_kernel(const GemmParam
     __syncthreads();
   }
 
-  gemm_epilogue<EPI, 2>(p, acc, bg, g, p0, n0, wave, wr, wc, li, lh, smem);
+  if constexpr (EPI == EPI_MAX_CF)
+    max_cf_epilogue<2>(p, acc, bg, p0, n0, wr, wc, li, lh, smem);
+  else
+    gemm_epilogue<EPI, 2>(p, acc, bg, g, p0, n0, wave, wr, wc, li, lh, smem);
 }
 
 // ---------------------------------------------------------------------------
@@ -864,8 +938,8 @@ __global__ __launch_bounds__(256, (NCB == 4 || LOADER == LOAD_INTERP || LOADER =
 
   ALoader<LOADER, RPT, RS> ld;
   ld.init(p, p0, g, t);
-  const int chunk = t & 7;    // A: 4-float chunk of the 32-wide K tile
-  const int srow = t >> 3;    // A: rows srow + 32 s
+  const int chunk = ALoader<LOADER, RPT, RS>::chunk(t);   // A: 4-float chunk of the 32-wide K tile
+  const int srow = ALoader<LOADER, RPT, RS>::srow(t);     // A: rows srow + 32 s
   const int wchunk = t & 3;   // W: 8-half chunk
   const int wrow = t >> 2;    // W: rows wrow + 64 s
   bool wok[WPT];
@@ -998,7 +1072,10 @@ __global__ __launch_bounds__(256, (NCB == 4 || LOADER == LOAD_INTERP || LOADER =
     const uint32_t wm = wave_max_u32(__float_as_uint(fmaxf(tmax, 0.f)));
     if (lane == 0) amax_publish(po.out_amax, wm, blockIdx.x * 4 + wave, p0, p_hi, p.rps);
   }
-  gemm_epilogue<EPI, NCB>(po, acc, bg, g, p0, n0, wave, wr, wc, li, lh, smemf);
+  if constexpr (EPI == EPI_MAX_CF)
+    max_cf_epilogue<NCB>(po, acc, bg, p0, n0, wr, wc, li, lh, smemf);
+  else
+    gemm_epilogue<EPI, NCB>(po, acc, bg, g, p0, n0, wave, wr, wc, li, lh, smemf);
 }
 
 template <int LOADER, int EPI, int NCB, int PL>
@@ -1744,7 +1821,8 @@ static int launch_gemm_f16x2(const GemmParams& p, int groups, hipStream_t st) {
   const char* rmode = s4g::knob("S4G_GEMM_RESIDENT");
   const bool no_resident = rmode && rmode[0] == '0';
   const bool any_resident = rmode && rmode[0] == '1';
-  if constexpr (EPI != EPI_CHANNEL_FIRST && LOADER != LOAD_INTERP && LOADER != LOAD_INTERP_ADD) {
+  if constexpr (EPI != EPI_CHANNEL_FIRST && EPI != EPI_MAX_CF && LOADER != LOAD_INTERP && LOADER != LOAD_INTERP_ADD &&
+                LOADER != LOAD_CHANNEL_FIRST) {
     // resident-A kernel: short contractions whose A panel fits LDS twice per CU
     const bool vec_ok = ((p.ldc | p.c_coff | p.c_gcol) & 3) == 0 &&
                         ((reinterpret_cast<uintptr_t>(p.out) & 15) == 0);
@@ -1868,7 +1946,7 @@ extern "C" int s4g_mlp_gemm_f32(const s4g_gemm_desc_t* d, s4g_stream_t stream) {
   GemmParams p;
   p.P = d->P; p.Cin = d->Cin; p.Kpad = d->Kpad; p.Cout = d->Cout; p.relu = d->relu;
   p.W = d->W; p.bias = d->bias;
-  p.A = d->A; p.lda = d->lda; p.a_coff = d->a_coff; p.a_gcol = d->a_gcol;
+  p.A = d->A; p.lda = d->lda; p.a_coff = d->a_coff; p.a_gcol = d->a_gcol; p.aL = d->a_L;
   p.gidx = d->gidx; p.feat = d->feat; p.xyz = d->xyz; p.ctr = d->ctr;
   p.Cf = d->Cf; p.N = d->N; p.M = d->M; p.K = d->K;
   p.mlp1 = (const float4*)d->mlp1_w;
@@ -1943,6 +2021,10 @@ extern "C" int s4g_mlp_gemm_f32(const s4g_gemm_desc_t* d, s4g_stream_t stream) {
     if (!d->nidx || !d->nw || !d->sparse || (d->C2 & 3) || (d->C1 & 3) ||
         (d->C1 > 0 && !d->dense) || d->N1 <= 0 || d->N2 <= 0 || d->groups != 1)
       return S4G_EINVAL;
+  } else if (d->loader == S4G_GEMM_LOAD_CHANNEL_FIRST) {
+    if (!d->A || d->Cin < 1 || d->a_L <= 0 || d->P % d->a_L || d->groups != 1 ||
+        d->Cin > (h2 ? d->Kpad16 : d->Kpad))
+      return S4G_EINVAL;
   } else {
     return S4G_EINVAL;
   }
@@ -1960,6 +2042,11 @@ extern "C" int s4g_mlp_gemm_f32(const s4g_gemm_desc_t* d, s4g_stream_t stream) {
     if (!d->out) return S4G_EINVAL;
   } else if (d->epilogue == S4G_GEMM_EPI_CHANNEL_FIRST) {
     if (d->cf_N <= 0 || d->groups != 1) return S4G_EINVAL;
+  } else if (d->epilogue == S4G_GEMM_EPI_MAX_CHANNEL_FIRST) {
+    // the atomicMax merge is on the bits of non-negative values: only after a ReLU
+    if (d->relu != 1 || d->K < 1 || d->M < 1 || d->P % ((int64_t)d->M * d->K) || d->groups != 1 || !d->out ||
+        d->W2_f16x2_frag || d->out2)
+      return S4G_EINVAL;
   } else {
     return S4G_EINVAL;
   }
@@ -2048,5 +2135,40 @@ extern "C" int s4g_mlp_gemm_f32(const s4g_gemm_desc_t* d, s4g_stream_t stream) {
   S4G_GEMM_CASE(LOAD_GATHER_ADD, EPI_MAX)
   S4G_GEMM_CASE(LOAD_INTERP_ADD, EPI_STORE)
 #undef S4G_GEMM_CASE
+  // the generic SharedMLP / SA path (ABI 14): f16x2 and fp32 only
+#define S4G_GEMM_CASE_CF(L, E)                                                           \
+  if (d->loader == L && d->epilogue == E)                                                \
+    return h2 ? launch_gemm_f16x2<L, E>(p, d->groups, st)                                \
+              : d->precision == S4G_GEMM_FP32 ? launch_gemm<L, E>(p, d->groups, st) : S4G_EUNSUPPORTED;
+  S4G_GEMM_CASE_CF(LOAD_CHANNEL_FIRST, EPI_STORE)
+  S4G_GEMM_CASE_CF(LOAD_CHANNEL_FIRST, EPI_CHANNEL_FIRST)
+  S4G_GEMM_CASE_CF(LOAD_CHANNEL_FIRST, EPI_MAX_CF)
+  S4G_GEMM_CASE_CF(LOAD_PLAIN, EPI_MAX_CF)
+#undef S4G_GEMM_CASE_CF
   return S4G_EUNSUPPORTED;
+}
+
+// Per-scene max |x| into (B, 64) uint32 slot rows (zeroed by the caller): the a_amax of an f16x2 launch whose input
+// no launch of ours produced.  Grid (wgs per scene, B); each wave leaves one atomicMax in slot (wg * 4 + wave) % 64.
+__global__ __launch_bounds__(256) void amax_per_scene_kernel(const float* __restrict__ x, int64_t n,
+                                                             uint32_t* __restrict__ slots) {
+  const int b = blockIdx.y;
+  const float* xs = x + (size_t)b * n;
+  float m = 0.f;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256)
+    m = fmaxf(m, fabsf(xs[i]));
+  const uint32_t wm = s4g::wave_max_u32(__float_as_uint(m));
+  if ((threadIdx.x & 63) == 0) atomicMax(slots + (size_t)b * 64 + ((blockIdx.x * 4 + (threadIdx.x >> 6)) & 63), wm);
+}
+
+extern "C" int s4g_amax_per_scene_f32(const float* x, int64_t B, int64_t n_per_scene, float* out_slots,
+                                      s4g_stream_t stream) {
+  if (B < 0 || n_per_scene < 0 || B > 65535 || ((!x || !out_slots) && B * n_per_scene > 0)) return S4G_EINVAL;
+  if (B == 0 || n_per_scene == 0) return S4G_OK;
+  const int64_t want = (n_per_scene + 256 * 16 - 1) / (256 * 16);   // ~16 elements per thread
+  const unsigned wgs = (unsigned)(want < 64 ? want : 64);
+  hipLaunchKernelGGL(amax_per_scene_kernel, dim3(wgs, (unsigned)B), dim3(256), 0, (hipStream_t)stream, x, n_per_scene,
+                     reinterpret_cast<uint32_t*>(out_slots));
+  S4G_LAUNCH_CHECK();
+  return S4G_OK;
 }

@@ -79,6 +79,26 @@ class FeatureInterpolator(nn.Module):
         return "num_neighbours={:d}, eps={}".format(self.num_neighbors, self._eps)
 
 
+def sample_and_group(sa, xyz, feature=None):
+    """The sample-and-group half of `PointNetSAModule.forward`: (new_xyz (B, 3, M), group_feature (B, C, M, K)).
+    Reads only `sa.num_centroids`, `sa.sampler`, `sa.grouper` and `sa.use_xyz`, so the reference's own SA instances
+    can call it too (`accelerate.py`)."""
+    if sa.num_centroids == 0:
+        # one group holding every point, centred at the origin (modules.py:224-231)
+        assert sa.grouper is None
+        new_xyz = xyz.new_zeros(xyz.size(0), 3, 1)
+        group_feature = feature.unsqueeze(2)
+        if sa.use_xyz:
+            group_feature = torch.cat([xyz.unsqueeze(2), group_feature], dim=1)
+    else:
+        if sa.num_centroids == -1:
+            new_xyz = xyz
+        else:
+            new_xyz = _F.gather_points(xyz, sa.sampler(xyz))
+        group_feature, _ = sa.grouper(new_xyz, xyz, feature, use_xyz=sa.use_xyz)
+    return new_xyz, group_feature
+
+
 class PointNetSAModule(nn.Module):
     """Sample (FPS) -> group (ball query) -> shared MLP -> max over neighbours."""
 
@@ -98,19 +118,7 @@ class PointNetSAModule(nn.Module):
             self.grouper = QueryGrouper(radius, num_neighbours)
 
     def forward(self, xyz, feature=None):
-        if self.num_centroids == 0:
-            # one group holding every point, centred at the origin (modules.py:224-231)
-            assert self.grouper is None
-            new_xyz = xyz.new_zeros(xyz.size(0), 3, 1)
-            group_feature = feature.unsqueeze(2)
-            if self.use_xyz:
-                group_feature = torch.cat([xyz.unsqueeze(2), group_feature], dim=1)
-        else:
-            if self.num_centroids == -1:
-                new_xyz = xyz
-            else:
-                new_xyz = _F.gather_points(xyz, self.sampler(xyz))
-            group_feature, _ = self.grouper(new_xyz, xyz, feature, use_xyz=self.use_xyz)
+        new_xyz, group_feature = sample_and_group(self, xyz, feature)
         new_feature = self.mlp(group_feature)
         new_feature, _ = torch.max(new_feature, 3)
         return new_xyz, new_feature
