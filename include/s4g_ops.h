@@ -76,32 +76,28 @@ extern "C" {
  *   S4G_BENCH_BACKEND=gloo; the oracle reads S4G_ORACLE_LIB / S4G_ORACLE_F64 -- test infrastructure, not the product.)
  *
  * A/B AND TEST KNOBS -- IGNORED unless the process sets S4G_TEST_KNOBS=1 (tests/conftest.py does; tools that set one set
- * it too) or the library is a -DS4G_VARIANTS measurement build (s4g_test_knobs_enabled() says which).  Round 6: a stray
+ * it too; s4g_test_knobs_enabled() says whether they are honoured).  Round 6: a stray
  * variable in a launcher's environment can no longer change which kernel a production rank runs.  Every alternative is
  * exact (same results; the defaults are the measured-fastest paths), so the switch can change speed, never values.
  *  library side (s4g::knob in csrc/s4g_common.h; per call unless noted):
  *   S4G_FPS_MODE=dense|pruned      FPS kernel for N <= 25 600: full scan | group-pruned (default: pruned
  *                                  above 10 240 points, and above 5 120 when M >= 2 048).  =dense also turns the L2-resident pruned kernel
  *                                  off for 25 600 < N <= 65 535 (the streaming kernel runs instead)
- *   S4G_FPS_DENSE_STEPS=k          first k picks by the full-scan kernel in front of the pruned one (0)
  *   S4G_BQ_MODE=scan|grid          ball query path (default: grid from 8 192 points)
- *   S4G_GRID_BUILD=loop            streaming grid build for every size (read once)
  *   S4G_NN_SPLIT=0                 3-NN: never the split scan for 24 <= N2 <= 2 048
- *   S4G_NN_CELL_FACTOR=f           3-NN operator API: cell edge = f x measured 3rd-neighbour spacing (1.75; once)
  *   S4G_INTERP_MODE=lane           three_interpolate: lane-per-point kernel instead of the LDS tile
  *   S4G_GEMM_SINGLE_CHAIN=0|1      plain single layers never / wherever supported on mlp_chain_kernel's first-layer
  *                                  form (default: where it measured faster: Cout >= 1024 or K >= 1024)
  *   S4G_MLP1_MFMA=0                first SA level's 3 -> C layer on the vector ALU (the chain kernel's loader) instead of
  *                                  one MFMA step inside the chain kernel (f16x2 form with rel_xyz4 records)
- *   measurement builds only: S4G_FPS_MODE=cluster|hybrid, S4G_BQ_MODE=cell (+ S4G_BQ_CELL_WGS), S4G_GEMM_RESIDENT=0|1
  *  host side (_cabi.knob; read when a FusedPointNet2 is built / an operator is called):
  *   S4G_SA_UNIQUE=0                first SA level contracts all K rows, padding copies included
  *   S4G_REL_XYZ=0                  first SA level's loader follows the indices itself
  *   S4G_SA_LINEAR_FIRST=0, S4G_FP_LINEAR_FIRST=0   no linear-layer-before-grouping / -interpolation
- *   S4G_FP_LOADER_ADD=auto|none|levels, S4G_FP_CHAIN_NEXT=0   where the FP sums are formed
- *   S4G_GEMM_FUSE2=0, S4G_GEMM_FUSE3=0, S4G_GEMM_FUSE512=0    layer chains as separate launches
+ *   S4G_FP_CHAIN_NEXT=0            the next FP level's linear-first layer as a launch of its own
+ *   S4G_GEMM_FUSE2=0               layer chains as separate launches
  *   S4G_MERGE_SHARED=0             sa{l}.0f and fp{f}.0d (same input tensor) as two launches instead of one
- *   S4G_HEADS_FUSED=0, S4G_HEADS_PRE=0   heads layer by layer / FP tail outside the heads launch
+ *   S4G_HEADS_PRE=0                FP tail outside the heads launch
  *   S4G_FPS_PREFIX=0               always sample SA levels 2 and 3 (no prefix proof)
  *   S4G_NN_MODE=scan               3-NN: never the cell-grid search
  *   S4G_PACKED_OUT=0               FusedPointNet2 returns four head tensors of their own instead of channel slices of one
@@ -123,13 +119,10 @@ typedef void *s4g_stream_t; /* hipStream_t */
 #define S4G_OP_THREE_NN 3
 
 int s4g_abi_version(void);
-/* ABI >= 8.  1 if the library is a measurement build (make HIPFLAGS_EXTRA=-DS4G_VARIANTS) that also
- * carries the measured-slower kernel variants of csrc/variants/ (two-CU / hybrid FPS for 51 200 points,
- * the cell-centric ball query, the resident-A single-layer contraction); 0 for the shipped library,
- * where S4G_FPS_MODE=cluster|hybrid, S4G_BQ_MODE=cell and S4G_GEMM_RESIDENT select nothing. */
+/* ABI >= 8.  Always 0: the library carries no kernel variants; kept because the symbol is part of the ABI. */
 int s4g_build_variants(void);
-/* 1 when the A/B / test knobs listed above are honoured in this process (S4G_TEST_KNOBS=1 in the environment, or a
- * measurement build); 0: the library ignores every one of them. */
+/* 1 when the A/B / test knobs listed above are honoured in this process (S4G_TEST_KNOBS=1 in the environment);
+ * 0: the library ignores every one of them. */
 int s4g_test_knobs_enabled(void);
 const char *s4g_error_string(int code);
 

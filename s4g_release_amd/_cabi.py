@@ -90,7 +90,7 @@ SIGNATURES = {
     "s4g_fps_prepass_f32": (_int, [_vp, _i64, _i64, _i64, _vp, _vp, _vp]),
     "s4g_fps_gather_ex_i32": (_int, [_vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _sz, _int, _vp]),
     "s4g_fps_prefix_check_f32": (_int, [_vp, _vp, _i64, _i64, _i64, _vp, _int, _vp]),
-    "s4g_build_variants": (_int, []),
+    "s4g_build_variants": (_int, []),     # always 0: no kernel variants; kept because the symbol is in the ABI
     "s4g_test_knobs_enabled": (_int, []),
     # double dispatch of the five operators (csrc/ops_f64.hip)
     "s4g_fps_f64": (_int, [_vp, _i64, _i64, _i64, _vp, _vp, _sz, _int, _vp]),

@@ -8,16 +8,10 @@ size_t ball_query_workspace_bytes(int64_t B, int64_t N, int64_t M, int64_t K);
 
 extern "C" int s4g_abi_version(void) { return S4G_ABI_VERSION; }
 
-// 1: a measurement build (-DS4G_VARIANTS) that also carries the measured-slower kernel variants
-extern "C" int s4g_build_variants(void) {
-#ifdef S4G_VARIANTS
-  return 1;
-#else
-  return 0;
-#endif
-}
+// Always 0: the library carries no kernel variants; the symbol stays because it has been exported since ABI 8
+extern "C" int s4g_build_variants(void) { return 0; }
 
-// 1: the A/B knobs of include/s4g_ops.h are being honoured in this process (S4G_TEST_KNOBS=1 or a measurement build)
+// 1: the A/B knobs of include/s4g_ops.h are being honoured in this process (S4G_TEST_KNOBS=1)
 extern "C" int s4g_test_knobs_enabled(void) { return s4g::test_knobs_enabled() ? 1 : 0; }
 
 extern "C" const char* s4g_error_string(int code) {

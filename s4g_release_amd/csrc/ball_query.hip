@@ -489,23 +489,17 @@ __global__ __launch_bounds__(64 * BQ_WAVES_PER_BLOCK) void bq_grid_query_kernel(
   }
 }
 
-#ifdef S4G_VARIANTS
-#include "variants/bq_cell.inc"
-#endif
-
 int launch_grid_build(const float* xyz, int64_t B, int64_t N, float inv_h, GridWs ws,
                       hipStream_t st, bool write_aos, const float* inv_h_dev) {
 #define S4G_GB_LAUNCH(P)                                                                          \
   hipLaunchKernelGGL(bq_grid_build_kernel<P>, dim3(GR_RANGES, (unsigned)B), dim3(GR_BUILD_THREADS), \
                      0, st, xyz, (int)N, inv_h, ws, write_aos ? 1 : 0, (const float*)nullptr, 0, \
                      CellWs{nullptr, nullptr, nullptr}, inv_h_dev)
-  // S4G_GRID_BUILD=loop: the streaming variant for every size.  The register-resident workgroups
+  // Selected by size: the streaming variant (0) above 25 points per thread.  The register-resident workgroups
   // (1024 threads x up to 128 registers) need a whole free CU: alone they are faster (36 -> 20 us at
   // 16 x 25 600 points), underneath a saturating contraction stream they wait longer for one
   // (ball query 0.19 -> 0.42 ms per batch; the step time does not move, geometry has slack there).
-  static const bool loop = [] { const char* e = s4g::knob("S4G_GRID_BUILD"); return e && e[0] == 'l'; }();
-  if (loop) S4G_GB_LAUNCH(0);
-  else if (N <= 8 * GR_BUILD_THREADS) S4G_GB_LAUNCH(8);
+  if (N <= 8 * GR_BUILD_THREADS) S4G_GB_LAUNCH(8);
   else if (N <= 25 * GR_BUILD_THREADS) S4G_GB_LAUNCH(25);
   else S4G_GB_LAUNCH(0);
 #undef S4G_GB_LAUNCH
@@ -529,13 +523,12 @@ int launch_grid_build_queries(const float* xyz, const float* ctr, int64_t B, int
   return S4G_OK;
 }
 
-enum { BQ_AUTO = 0, BQ_SCAN = 1, BQ_GRID = 2, BQ_CELL = 3 };
+enum { BQ_AUTO = 0, BQ_SCAN = 1, BQ_GRID = 2 };
 
-static int bq_mode() {  // S4G_BQ_MODE=scan|grid|cell|auto (tuning / test knob, read per call)
+static int bq_mode() {  // S4G_BQ_MODE=scan|grid|auto (tuning / test knob, read per call)
   const char* e = s4g::knob("S4G_BQ_MODE");
   if (e && e[0] == 's') return BQ_SCAN;
   if (e && e[0] == 'g') return BQ_GRID;
-  if (e && e[0] == 'c') return BQ_CELL;
   return BQ_AUTO;
 }
 
@@ -543,25 +536,13 @@ static bool bq_use_grid(int64_t N, int64_t K) {
   if (N > GR_MAX_POINTS || K > 1024) return false;
   const int mode = bq_mode();
   if (mode == BQ_SCAN) return false;
-  if (mode == BQ_GRID || mode == BQ_CELL) return true;
+  if (mode == BQ_GRID) return true;
   return N >= 8192;
-}
-
-// centre-quad query instead of the per-centre one (needs the centres binned too).
-// OPT-IN (S4G_BQ_MODE=cell): exact, but as built it is slower than the per-centre
-// kernel (SA1, 16 scenes: 0.142 ms against 0.116 ms) -- see the CELL path's header.
-static bool bq_use_cell(int64_t M) {
-#ifdef S4G_VARIANTS
-  return bq_mode() == BQ_CELL && M >= 1 && M < (1 << 24);
-#else
-  (void)M;
-  return false;   // the cell-centric kernel is in measurement builds only: S4G_BQ_MODE=cell then means grid
-#endif
 }
 
 size_t ball_query_workspace_bytes(int64_t B, int64_t N, int64_t M, int64_t K) {
   if (!bq_use_grid(N, K)) return 0;
-  return grid_ws_bytes(B, N) + (bq_use_cell(M) ? cell_ws_bytes(B, M) : 0);
+  return grid_ws_bytes(B, N);
 }
 
 template <typename IdxT>
@@ -602,35 +583,6 @@ static int ball_query_dispatch(const float* xyz, const float* ctr, int64_t B,
   const int words = (int)((N + 31) / 32);
   int wpl = (words + 63) / 64;
   if ((wpl & 1) == 0) ++wpl;  // odd stride: conflict-free per-lane word runs
-#ifdef S4G_VARIANTS
-  if (bq_use_cell(M) && ws_bytes >= grid_ws_bytes(B, N) + cell_ws_bytes(B, M)) {
-    const CellWs cw = cell_ws_carve((char*)ws + grid_ws_bytes(B, N), B, M);
-    if (int rc = launch_grid_build_queries(xyz, ctr, B, N, M, inv_h, g, cw, st, false)) return rc;
-    // workgroups per scene: a workgroup strides over the scene's non-empty centre quads
-    int64_t wps = 4096 / B;
-    if (const char* e = s4g::knob("S4G_BQ_CELL_WGS")) wps = atoi(e);
-    if (wps < 32) wps = 32;
-    const int64_t max_quads = (M < GR_RANGES * GR_RANGE_SLOTS / 4) ? M : GR_RANGES * GR_RANGE_SLOTS / 4;
-    if (wps > max_quads) wps = max_quads;
-    const int per = 4 * BQC_THREADS;  // bitmap words: multiple of 4 per thread
-    const int bmw = (words + per - 1) / per * per;
-    const size_t clds = sizeof(uint32_t) * (size_t)(bmw + bmw / 2 + 4 * BQC_WIN + 8 +
-                                                    BQC_WAVES * (grouped ? 4 : 1) * ((K + 3) & ~3));
-    const dim3 cgrid((unsigned)wps, (unsigned)B);
-#define S4G_BQC_LAUNCH(F, G)                                                                 \
-  hipLaunchKernelGGL((bq_cell_query_kernel<F, IdxT, G>), cgrid, dim3(BQC_THREADS), clds, st, \
-                     xyz, (int)N, (int)M, r2, inv_h, (int)K, g, cw, idx, cnt, grouped, bmw,  \
-                     (int)wps)
-    if (grouped) {
-      if (fmad) S4G_BQC_LAUNCH(true, true); else S4G_BQC_LAUNCH(false, true);
-    } else {
-      if (fmad) S4G_BQC_LAUNCH(true, false); else S4G_BQC_LAUNCH(false, false);
-    }
-#undef S4G_BQC_LAUNCH
-    S4G_LAUNCH_CHECK();
-    return S4G_OK;
-  }
-#endif
   if (int rc = launch_grid_build(xyz, B, N, inv_h, g, st, grouped != nullptr)) return rc;
   const size_t lds = sizeof(uint32_t) * BQ_WAVES_PER_BLOCK * (size_t)(64 * wpl + ((K + 3) & ~3));
 #define S4G_BQ_LAUNCH4(F, G, W, C)                                                        \

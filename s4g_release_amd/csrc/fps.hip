@@ -19,9 +19,7 @@
 //   * fps_pruned_l2_kernel  25 600 < N <= 51 200 (default there): the same, with only the
 //                           min-distances resident and the coordinates of a touched group read
 //                           from the Morton-sorted records in L2 -- one CU per scene;
-//   * fps_stream_kernel     any other size (and 25 600 < N <= 51 200 without a workspace); the two full-scan
-//                           kernels for that range (variants/fps_fullscan_51k.inc: S4G_FPS_MODE=cluster|hybrid)
-//                           are compiled into measurement builds only (-DS4G_VARIANTS).
+//   * fps_stream_kernel     any other size (and 25 600 < N <= 65 535 without a workspace or with M < 64).
 // The reference's tie rule is reproduced exactly through a composite key: maximise d, then
 // minimise (bitrev_{log2 bs}(j mod bs) << 23 | j), where bs = clamp(pow2ceil(N),16,512) is the
 // REFERENCE's block size (sampling_kernel.cu:34-42,148-167) -- see SURVEY.md Appendix A.1.  In
@@ -297,7 +295,8 @@ __global__ __launch_bounds__(THREADS) void fps_reg_kernel(
     const float* __restrict__ xyz, int N, int M, IdxT* __restrict__ idx,
     float* __restrict__ ctr, int lg_bs, int M_run, float* __restrict__ md_out, FpsExtra ex) {
   // M_run <= M steps are computed (outputs keep stride M); md_out (or NULL) receives the
-  // running min-distances afterwards -- the hand-over to fps_pruned_kernel
+  // running min-distances afterwards.  launch_fps always passes M and NULL: the parameters are
+  // kept because the kernel compiled without them needs more VGPRs in its <256, 1> / <512, 1> forms
   constexpr int WAVES = THREADS / 64;
   __shared__ FpsSlot slots[2][FPS_MAX_WAVES];
   const int b = blockIdx.x;
@@ -428,10 +427,6 @@ __global__ __launch_bounds__(THREADS) void fps_reg_kernel(
   }
 }
 
-#ifdef S4G_VARIANTS
-#include "variants/fps_fullscan_51k.inc"
-#endif
-
 // Streaming fallback: any N < 2^23.  min-distance in `temp` (B,N) fp32.
 template <bool FMAD, typename IdxT>
 __global__ __launch_bounds__(FPS_THREADS) void fps_stream_kernel(
@@ -514,10 +509,9 @@ __global__ __launch_bounds__(FPS_THREADS) void fps_stream_kernel(
 // their min-distances and Mg bit for bit, so the selected index sequence is the
 // one of the full scan (tests compare against the oracle).  On the bench scenes a
 // centroid touches 5.3 of 400 groups on average (8.7 in round 2's Morton order).  The
-// kernel starts by itself from +inf min-distances (md_in == NULL; round 3 -- measured
-// equal alone, and one launch of a whole-CU workgroup fewer inside a pipelined step);
-// S4G_FPS_DENSE_STEPS = n > 1 has the full-scan kernel run the first n steps and hand its
-// min-distances over through the workspace, as rounds 1-2 did.  Updates are dispatched by straight-line
+// kernel starts by itself from +inf min-distances (round 3 -- measured equal to a full-scan
+// front alone, and one launch of a whole-CU workgroup fewer inside a pipelined step).
+// Updates are dispatched by straight-line
 // guarded blocks (one rarely-taken scalar branch per 8 slots, one per slot) with static
 // register indices; a group's maximum is only re-reduced when a point that held it came
 // closer; the winner's slot is fetched by one walk of a 6-level scalar branch tree.
@@ -526,7 +520,7 @@ __global__ __launch_bounds__(FPS_THREADS) void fps_stream_kernel(
 // that group that hold it (static register index through a scalar branch tree),
 // original index and tie key from an LDS table.
 // ---------------------------------------------------------------------------
-constexpr int FPS_DENSE_STEPS = 48;
+constexpr int FPS_PRUNED_MIN_PICKS = 48;   // the pruned kernels pay from more picks than this (launch_fps)
 
 __device__ __forceinline__ uint32_t f32_ordered(float v) {   // order-preserving float -> uint
   const uint32_t b = __float_as_uint(v);
@@ -1040,15 +1034,16 @@ __global__ __launch_bounds__(THREADS) void fps_pruned_kernel(const float* __rest
     x[p] = px[j];
     y[p] = py[j];
     z[p] = pz[j];
-    // min-distances after the first i0 steps (full-scan kernel); padding lanes sit at 0:
-    // never a maximum unless every real point is at 0 too
+    // md_in (or NULL) = min-distances after the first i0 steps; launch_fps always passes NULL and 1 (the
+    // parameters are kept: without them the kernel needs more VGPRs, <512, 32, true> one wave per SIMD
+    // fewer).  Padding lanes sit at 0: never a maximum unless every real point is at 0 too
     md[p] = ok ? (md_in ? md_in[(size_t)b * N + j] : __builtin_inff()) : 0.0f;
     orig[s] = (uint16_t)j;
   }
   const uint32_t rkey = (__brev((uint32_t)t & bs_mask) >> (32 - lg_bs)) << 23;   // all-zero case only
   __syncthreads();
 
-  // md_in == NULL: no full-scan kernel ran before (i0 == 1): point 0 is the first centroid and every
+  // md_in == NULL (i0 == 1): point 0 is the first centroid and every
   // min-distance starts at +inf, so the first update touches every group
   int cur = md_in ? (int)out[i0 - 1] : 0;
   float cx = px[cur], cy = py[cur], cz = pz[cur];
@@ -1344,7 +1339,7 @@ __global__ __launch_bounds__(THREADS) void fps_pruned_kernel(const float* __rest
 // the Morton-sorted (x, y, z, original index) records (L2-resident: 0.8 MB per scene), issued
 // for a block of eight slots at a time; the candidate's record is read the same way.  A step
 // costs two dependent L2 round trips more than the register-resident kernel, but it needs ONE CU
-// per scene where the full-scan cluster kernel holds two (3.1 us/step each): a 32-scene batch
+// per scene where a two-CU full scan holds two (3.1 us/step each): a 32-scene batch
 // of 51 200-point clouds took 30 % of the chip's CU time for FPS alone.  No dense first phase:
 // the min-distances start at +inf, so the first steps touch every group (13 blocks of loads per
 // step) and the count decays within a few dozen steps.
@@ -1571,7 +1566,6 @@ static int fps_l2_slots(int64_t N) { return N <= FPS_L2_CAP ? 100 : 128; }
 
 struct FpsSortWs {
   float* gbox;      // [B][G][6] boxes of the 64-point groups
-  float* md;        // [B][N] min-distances handed over by the full-scan kernel (S4G_FPS_DENSE_STEPS > 1)
   int* val_out;     // [B][N] the pre-pass's permutation
   float4* aos;      // cell-ordered (x, y, z, index) records: fps_pruned_l2_kernel only (N > 25 600)
   size_t total;
@@ -1592,19 +1586,17 @@ static FpsSortWs fps_sort_ws(void* base, int64_t B, int64_t N) {
   const int64_t l2_groups = 8 * (int64_t)fps_l2_slots(N);
   const int64_t gbox_groups = (N + 63) / 64 + 256 > l2_groups ? (N + 63) / 64 + 256 : l2_groups;
   w.gbox = (float*)take(sizeof(float) * 6 * B * gbox_groups);
-  w.md = (float*)take(sizeof(float) * n);
   w.val_out = (int*)take(sizeof(int) * n);
   w.aos = N > (int64_t)512 * 50 ? (float4*)take(sizeof(float4) * (size_t)B * 512 * fps_l2_slots(N)) : nullptr;
   w.total = off;
   return w;
 }
 
-// 25 600 < N <= 51 200: the one-CU pruned kernel with coordinates in L2 (default),
-// S4G_FPS_MODE=cluster the two-CU full scan (opt-in, B <= 128), =hybrid the one-CU full scan
+// 25 600 < N <= 65 535: the one-CU pruned kernel with coordinates in L2 (S4G_FPS_MODE=dense: the streaming kernel)
 static bool fps_use_pruned_l2(int64_t N, int64_t M) {
   if (N <= (int64_t)512 * 50 || N > FPS_L2_CAP_BIG || M < 64) return false;
   const char* e = s4g::knob("S4G_FPS_MODE");
-  return !(e && (e[0] == 'c' || e[0] == 'h' || e[0] == 'd'));
+  return !(e && e[0] == 'd');
 }
 
 // M < 0: "may the pruned kernel run for this N" (workspace sizing, which does not know M)
@@ -1633,23 +1625,6 @@ static int ref_block_lg(int64_t n) {
   if (cnt < 4) cnt = 4;
   return cnt;
 }
-
-// The two-CU kernel is OPT-IN (S4G_FPS_MODE=cluster) and only taken when both workgroups of every
-// scene can be resident at once (2 B workgroups of 512 threads, one per CU, on 256 CUs): its two
-// halves spin on each other, and HIP guarantees no co-residency beyond what fits the chip.  A
-// partner that never answers sets the error word AND turns every later index of that scene into
-// -1 (the caller sees an impossible index instead of a plausible wrong one).  Everything else in
-// this size range that cannot take the pruned kernel (M < 64, workspace too small) runs the
-// single-CU hybrid kernel, which has no such requirement.
-#ifdef S4G_VARIANTS
-static bool fps_use_cluster(int64_t B) {
-  const char* e = s4g::knob("S4G_FPS_MODE");
-  return e && e[0] == 'c' && 2 * B <= 256;
-}
-static size_t fps_cluster_ws_bytes(int64_t B) { return (size_t)B * 4 * sizeof(FpsXch) + 64; }
-#else
-static size_t fps_cluster_ws_bytes(int64_t) { return 0; }
-#endif
 
 // ---------------------------------------------------------------------------
 // FPS of an FPS-ordered set is its own prefix.  Let c_0 .. c_{M1-1} be the picks of one FPS run in
@@ -1720,38 +1695,44 @@ static int launch_fps(const float* xyz, int64_t B, int64_t N, int64_t M,
   const int lg = ref_block_lg(N);
   const dim3 grid((unsigned)B);
 
-  // opt-in pruned variant: Morton order + group boxes, the first FPS_DENSE_STEPS steps by
-  // the full-scan kernel (which leaves its min-distances in the workspace), the rest pruned
-  FpsSortWs w = {};
-  bool pruned = false;
-  if (fps_use_pruned(N, M) && M > FPS_DENSE_STEPS && B < (1 << 16)) {
-    w = fps_sort_ws(ws, B, N);
-    pruned = ws && ws_bytes >= w.total;
+  // pruned kernel: spatial order + group boxes by the pre-pass, then every pick (it starts from +inf
+  // min-distances by itself)
+  if (fps_use_pruned(N, M) && M > FPS_PRUNED_MIN_PICKS && B < (1 << 16)) {
+    const FpsSortWs w = fps_sort_ws(ws, B, N);
+    if (ws && ws_bytes >= w.total) {
+      const int G = 8 * (N <= 512 * 10 ? 10 : N <= 512 * 20 ? 20 : N <= 512 * 32 ? 32 : 50);   // groups of the pruned launch below
+      if (int rc = launch_fps_cell_sort(xyz, B, N, G, w.val_out, w.gbox, nullptr, 0, stream)) return rc;
+  // up to four picks per exchange (one and two -- rounds 1 and 2 -- measured slower: 6.7 / 6.0 / 4.0 ms)
+#define S4G_FPS_PRUNED_LAUNCH(T, P, S)                                                             \
+  {                                                                                                \
+    static LdsAttrCache lds_cache;                                                                 \
+    if (int rc = allow_dynamic_lds(reinterpret_cast<const void*>(&fps_pruned_kernel<T, P, FMAD, IdxT, S>), lds, lds_cache)) return rc;  \
+    hipLaunchKernelGGL((fps_pruned_kernel<T, P, FMAD, IdxT, S>), grid, dim3(T), lds, stream, xyz,  \
+                       w.val_out, w.gbox, (const float*)nullptr, 1, (int)N, (int)M, idx, ctr, lg,  \
+                       ex.dist);                                                                   \
   }
-  int m_run = (int)M;
-  float* md_out = nullptr;
-  // steps the full-scan kernel runs in front of the pruned one (S4G_FPS_DENSE_STEPS; 0 = none: the pruned
-  // kernel starts from +inf min-distances by itself)
-  int dense_steps = 0;
-  if (const char* e = s4g::knob("S4G_FPS_DENSE_STEPS")) dense_steps = atoi(e) > 1 ? atoi(e) : 0;
-  if (dense_steps >= M) pruned = false;
-  if (pruned) {
-    const int G = 8 * (N <= 512 * 10 ? 10 : N <= 512 * 20 ? 20 : N <= 512 * 32 ? 32 : 50);   // groups of the pruned launch below
-    if (int rc = launch_fps_cell_sort(xyz, B, N, G, w.val_out, w.gbox, nullptr, 0, stream)) return rc;
-    m_run = dense_steps;
-    md_out = w.md;
+#define S4G_FPS_PRUNED(T, P)                                                                       \
+  if (N <= (int64_t)T * P) {                                                                       \
+    const size_t lds = (sizeof(uint16_t) + sizeof(float)) * T * P;   /* original indices + the tie path's min-distance columns */ \
+    S4G_FPS_PRUNED_LAUNCH(T, P, 4)                                                                 \
+    S4G_LAUNCH_CHECK();                                                                            \
+    return S4G_OK;                                                                                 \
+  }
+      S4G_FPS_PRUNED(512, 10)
+      S4G_FPS_PRUNED(512, 20)
+      S4G_FPS_PRUNED(512, 32)
+      S4G_FPS_PRUNED(512, 50)   // (fps_use_pruned: N <= 512 * 50, so one of the four has returned)
+#undef S4G_FPS_PRUNED
+#undef S4G_FPS_PRUNED_LAUNCH
+    }
   }
 
-  bool launched = pruned && dense_steps == 0;   // (no full-scan launch in front of the pruned kernel)
-  // the per-scene skip flags are honoured by the full-scan kernel when it IS the sampler (N <= 10 240);
-  // as the dense front of the pruned kernel it must run every scene, or the pruned steps would start
-  // from min-distances nobody wrote
-  const FpsExtra ex_reg = pruned ? FpsExtra{ex.dist, nullptr} : ex;
+  bool launched = false;
 #define S4G_FPS_CASE(T, P)                                                   \
   if (!launched && N <= (int64_t)T * P) {                                    \
     hipLaunchKernelGGL((fps_reg_kernel<T, P, FMAD, IdxT>), grid, dim3(T), 0, \
-                       stream, xyz, (int)N, (int)M, idx, ctr, lg, m_run,     \
-                       md_out, ex_reg);                                      \
+                       stream, xyz, (int)N, (int)M, idx, ctr, lg, (int)M,    \
+                       (float*)nullptr, ex);                                 \
     S4G_LAUNCH_CHECK();                                                      \
     launched = true;                                                         \
   }
@@ -1765,30 +1746,6 @@ static int launch_fps(const float* xyz, int64_t B, int64_t N, int64_t M,
   S4G_FPS_CASE(512, 32)
   S4G_FPS_CASE(512, 50)
 #undef S4G_FPS_CASE
-  if (launched && pruned) {
-  // up to four picks per exchange (one and two -- rounds 1 and 2 -- measured slower: 6.7 / 6.0 / 4.0 ms)
-#define S4G_FPS_PRUNED_LAUNCH(T, P, S)                                                             \
-  {                                                                                                \
-    static LdsAttrCache lds_cache;                                                                 \
-    if (int rc = allow_dynamic_lds(reinterpret_cast<const void*>(&fps_pruned_kernel<T, P, FMAD, IdxT, S>), lds, lds_cache)) return rc;  \
-    hipLaunchKernelGGL((fps_pruned_kernel<T, P, FMAD, IdxT, S>), grid, dim3(T), lds, stream, xyz,  \
-                       w.val_out, w.gbox, dense_steps ? w.md : nullptr, dense_steps ? dense_steps : 1, \
-                       (int)N, (int)M, idx, ctr, lg, ex.dist);                                     \
-  }
-#define S4G_FPS_PRUNED(T, P)                                                                       \
-  if (N <= (int64_t)T * P) {                                                                       \
-    const size_t lds = (sizeof(uint16_t) + sizeof(float)) * T * P;   /* original indices + the tie path's min-distance columns */ \
-    S4G_FPS_PRUNED_LAUNCH(T, P, 4)                                                                 \
-    S4G_LAUNCH_CHECK();                                                                            \
-    return S4G_OK;                                                                                 \
-  }
-    S4G_FPS_PRUNED(512, 10)
-    S4G_FPS_PRUNED(512, 20)
-    S4G_FPS_PRUNED(512, 32)
-    S4G_FPS_PRUNED(512, 50)
-#undef S4G_FPS_PRUNED
-#undef S4G_FPS_PRUNED_LAUNCH
-  }
   if (launched) return S4G_OK;
   if (fps_use_pruned_l2(N, M) && B < (1 << 16)) {
     const FpsSortWs w2 = fps_sort_ws(ws, B, N);
@@ -1806,27 +1763,7 @@ static int launch_fps(const float* xyz, int64_t B, int64_t N, int64_t M,
     }
   }
   if (ex.dist) return S4G_EUNSUPPORTED;   // the remaining kernels do not report pick distances
-#ifdef S4G_VARIANTS
-  // opt-in: two workgroups per scene, all points in registers, winners exchanged through L2 once
-  // per step (see fps_use_cluster for the co-residency requirement)
-  if (N <= (int64_t)512 * 100 && fps_use_cluster(B) && ws && ws_bytes >= fps_cluster_ws_bytes(B)) {
-    FpsXch* xch = (FpsXch*)ws;
-    int* err = (int*)((char*)ws + (size_t)B * 4 * sizeof(FpsXch));
-    const hipError_t e = hipMemsetAsync(ws, 0, fps_cluster_ws_bytes(B), stream);
-    if (e != hipSuccess) return (int)e;
-    hipLaunchKernelGGL((fps_cluster_kernel<512, 50, FMAD, IdxT>), dim3((unsigned)(2 * B)), dim3(512), 0,
-                       stream, xyz, (int)N, (int)M, idx, ctr, lg, xch, err);
-    S4G_LAUNCH_CHECK();
-    return S4G_OK;
-  }
-  if (N <= (int64_t)512 * 100) {   // x + min-distance in registers, y / z streamed from L2
-    hipLaunchKernelGGL((fps_hybrid_kernel<512, 100, 10, FMAD, IdxT>), grid, dim3(512), 0, stream, xyz,
-                       (int)N, (int)M, idx, ctr, lg);
-    S4G_LAUNCH_CHECK();
-    return S4G_OK;
-  }
-#endif
-  // (default build: what the pruned kernel cannot take in this range -- M < 64, no workspace -- streams)
+  // (what the pruned kernel cannot take in this range -- M < 64, no workspace -- streams)
   if (ws_bytes < (size_t)B * (size_t)N * sizeof(float) || ws == nullptr)
     return S4G_EWORKSPACE;
   hipLaunchKernelGGL((fps_stream_kernel<FMAD, IdxT>), grid, dim3(FPS_THREADS), 0, stream,
@@ -1838,11 +1775,7 @@ static int launch_fps(const float* xyz, int64_t B, int64_t N, int64_t M,
 size_t fps_workspace_bytes(int64_t B, int64_t N) {
   if (N <= 0 || B <= 0) return 0;
   if (N <= (int64_t)512 * 50) return fps_use_pruned(N, -1) ? fps_sort_ws(nullptr, B, N).total : 0;
-  if (N <= FPS_L2_CAP_BIG) {   // sort buffers + sorted records of the pruned kernel / the cluster kernel's exchange slots
-    const size_t c = fps_cluster_ws_bytes(B);
-    const size_t l2 = fps_sort_ws(nullptr, B, N).total;
-    return l2 > c ? l2 : c;
-  }
+  if (N <= FPS_L2_CAP_BIG) return fps_sort_ws(nullptr, B, N).total;   // sort buffers + sorted records of the pruned kernel
   return (size_t)B * (size_t)N * sizeof(float);
 }
 

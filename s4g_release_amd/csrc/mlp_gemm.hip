@@ -28,8 +28,6 @@
 //   mlp_gemm_bf16x3_kernel           three bf16 planes, six products: exact-class alternative
 //   mlp_gemm_f16x2_kernel            two fp16 planes, three products (fp32-class; PL = 1: one bf16
 //                                    plane): the tiled single-layer form, both operands through LDS
-//   mlp_gemm_f16x2_resident_kernel   short contractions with the A panel resident in LDS (measurement
-//                                    builds only: variants/gemm_resident.inc)
 //   mlp_chain_kernel                 two or three layers per launch, intermediates in LDS, W streamed
 //                                    in MFMA-fragment order: the kernels the shipped network runs on
 // (the four heads as one launch live in mlp_heads.hip, helpers shared by both in mlp_common.h).
@@ -132,7 +130,7 @@ struct GemmParams {
   float a_amax_floor;
   uint32_t* out_amax;          // 64 slots or NULL
   int rps;                     // loader rows per scene: slot row s of a_amax / out_amax belongs to scene s (0: one row)
-  const uint16_t* Wfrag;       // f16x2 planes in MFMA-fragment order (resident-A kernel) or NULL
+  const uint16_t* Wfrag;       // f16x2 planes in MFMA-fragment order (mlp_chain_kernel) or NULL
   const float* lbias;          // INTERP_ADD loader: bias of the layer whose output the loader forms
   // fused second layer (mlp_chain_kernel): out = max_K relu(bn(W2 relu(bn(W A))))
   const uint16_t* Wfrag2;
@@ -1093,21 +1091,15 @@ static int launch_gemm_f16x2_cfg(GemmParams p, int groups, hipStream_t st) {
   return S4G_OK;
 }
 
-#ifdef S4G_VARIANTS
-#define S4G_VARIANT_PART 1
-#include "variants/gemm_resident.inc"
-#undef S4G_VARIANT_PART
-#endif
-
 // ---------------------------------------------------------------------------
 // f16x2, two fused layers (the last two layers of an SA level whose widths allow it:
-// K = 128 -> 128 -> Cout2, max over the 64 neighbours): the resident-A kernel run twice
-// on ONE LDS panel.  A workgroup owns 128 positions (two centroids).  Phase 1 contracts
+// K = 128 -> 128 -> Cout2, max over the 64 neighbours): a resident-A contraction (the
+// A panel stays in LDS, W streams from memory in MFMA-fragment order) run twice on ONE LDS panel.  A workgroup owns 128 positions (two centroids).  Phase 1 contracts
 // the loader's panel with W (operands swapped: a lane ends up with 4 consecutive channels
 // of one position), applies scale / bias / ReLU, finds the TILE maximum (one barrier --
 // which is also the point where nobody reads the old panel any more), splits the
 // activations with the tile's own power-of-two scale and writes them over the panel.
-// Phase 2 is the resident kernel's strip loop on that panel with the max epilogue.  The
+// Phase 2 is the same strip loop on that panel with the max epilogue.  The
 // 128-channel intermediate never leaves the CU: no 2.7 GB store + load + re-split, no
 // amax round trip through HBM (a per-tile scale is as exact as the per-tensor one: both
 // are powers of two undone in the epilogue).
@@ -1805,38 +1797,9 @@ static int launch_mlp_chain(const GemmParams& p, int groups, hipStream_t st) {
   return S4G_OK;
 }
 
-#ifdef S4G_VARIANTS
-#define S4G_VARIANT_PART 2
-#include "variants/gemm_resident.inc"
-#undef S4G_VARIANT_PART
-#endif
-
 template <int LOADER, int EPI, int PL = 2>
 static int launch_gemm_f16x2(const GemmParams& p, int groups, hipStream_t st) {
   constexpr int force = 0;   // (tile width by shape; forcing it was a tuning knob of round 1)
-#ifdef S4G_VARIANTS
-  // S4G_GEMM_RESIDENT=0 never / 1 whenever the shape qualifies / unset: only where it
-  // measured faster than the tiled kernel (Cout >= 1024: +6 %; short strips lose to
-  // the per-workgroup prologue)
-  const char* rmode = s4g::knob("S4G_GEMM_RESIDENT");
-  const bool no_resident = rmode && rmode[0] == '0';
-  const bool any_resident = rmode && rmode[0] == '1';
-  if constexpr (EPI != EPI_CHANNEL_FIRST && EPI != EPI_MAX_CF && LOADER != LOAD_INTERP && LOADER != LOAD_INTERP_ADD &&
-                LOADER != LOAD_CHANNEL_FIRST) {
-    // resident-A kernel: short contractions whose A panel fits LDS twice per CU
-    const bool vec_ok = ((p.ldc | p.c_coff | p.c_gcol) & 3) == 0 &&
-                        ((reinterpret_cast<uintptr_t>(p.out) & 15) == 0);
-    if (PL == 2 && !no_resident && !force && !p.out2 && p.Wfrag && (EPI != EPI_STORE || vec_ok) &&
-        (EPI != EPI_MAX || p.K == 64) && (any_resident || p.Cout >= 1024)) {
-      if (p.Kpad16 == 256 && p.Cout % 256 == 0)
-        return launch_gemm_f16x2_resident<LOADER, EPI, 1, 256>(p, groups, st);
-      if (p.Kpad16 == 128 && p.Cout % 256 == 0)
-        return launch_gemm_f16x2_resident<LOADER, EPI, 1, 128>(p, groups, st);
-      if (p.Kpad16 == 128 && p.Cout % 128 == 0)
-        return launch_gemm_f16x2_resident<LOADER, EPI, 2, 128>(p, groups, st);
-    }
-  }
-#endif
   // the INTERP / GATHER loaders hold too much per-row state for the wide tile's
   // 128 accumulator registers (they would spill)
   // ... and 256-wide tiles only pay when they still fill the chip twice over: measured on the

@@ -618,7 +618,7 @@ static int launch_three_nn_grid(const float* q, const float* k, int64_t B, int64
   float* cell_dev = nullptr;   // header words 4, 5 of the fail list
   if (auto_cell) {
     cell_dev = reinterpret_cast<float*>(fail_count + 4);
-    static const float factor = [] { const char* e = s4g::knob("S4G_NN_CELL_FACTOR"); return e ? (float)atof(e) : 1.75f; }();
+    constexpr float factor = 1.75f;   // cell edge = factor x measured 3rd-neighbour spacing
     hipLaunchKernelGGL(nn_auto_cell_kernel, dim3(NN_SAMPLES), dim3(64), 0, st, k, (int)B, (int)N2, fail_count, factor);
     S4G_LAUNCH_CHECK();
     cell = 1.0f;

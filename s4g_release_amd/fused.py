@@ -202,16 +202,9 @@ class FusedPointNet2:
         self.dense_streams = max(1, int(os.environ.get("S4G_DENSE_STREAMS", "1")))
         # S4G_GEMM_FUSE2=0: never fuse the last two layers of an SA level into one launch
         self.fuse2 = _cabi.knob("S4G_GEMM_FUSE2", "1") != "0"
-        self.fuse3 = _cabi.knob("S4G_GEMM_FUSE3", "1") != "0"   # + first head layer
         # S4G_FP_LINEAR_FIRST=0: interpolate first, like the reference (fused into the
         # contraction's loader); default: first FP layer before the interpolation
         self.fp_linear_first = _cabi.knob("S4G_FP_LINEAR_FIRST", "1") != "0"
-        # FP levels whose interpolate + add + ReLU happens in the next launch's loader:
-        # S4G_FP_LOADER_ADD = "auto" (default: where that launch is a fused chain, whose panel is
-        # loaded once -- the tiled kernel would repeat the gathers per column tile: measured
-        # 0.41 ms against 0.14 + 0.18 ms at FP level 1), "none", or a comma list of levels
-        v = _cabi.knob("S4G_FP_LOADER_ADD", "auto")
-        self.fp_loader_add = v if v in ("auto", "none") else set(int(t) for t in v.split(",") if t)
         self.geo_streams = max(1, int(os.environ.get("S4G_GEO_STREAMS", "2")))
         self.rel_xyz = _cabi.knob("S4G_REL_XYZ", "1") != "0"
         # first SA level on a centroid's DISTINCT rows only (ball_query pads short balls with copies of the
@@ -326,11 +319,11 @@ class FusedPointNet2:
         self.sigmoid_from = sum(chans[:3])
         self._streams = None
         # all four heads as ONE launch (s4g_heads_chain_f32: input panel and every hidden
-        # activation stay in LDS) where the widths are the shipped ones; S4G_HEADS_FUSED=0 keeps
-        # the layer-chain launches
+        # activation stay in LDS) where the widths are the shipped ones; the layer-chain launches
+        # serve the other precisions and widths
         hl = self.head_layers
         self.heads_fused = None
-        if (_cabi.knob("S4G_HEADS_FUSED", "1") != "0" and precision in ("f16x2", "bf16") and depth == 4 and
+        if (precision in ("f16x2", "bf16") and depth == 4 and
                 hl[0].cin == 256 and hl[0].cout == 4 * 512 and
                 [(l.cout, l.cin, l.groups) for l in hl[1:]] == [(256, 512, 4), (256, 256, 4), (128, 256, 4)] and
                 cl == 128 and max(chans) <= 32 and len(chans) == 4):
@@ -382,10 +375,6 @@ class FusedPointNet2:
         if not (self.precision in ("f16x2", "bf16") and self.fuse2 and l1.groups == l2.groups and
                 l2.cin == c and l2.kpad16 == c and l2.cout % 64 == 0 and
                 l1.Wfrag is not None and l2.Wfrag is not None):
-            return False
-        if c == 512 and _cabi.knob("S4G_GEMM_FUSE512", "1") == "0":
-            return False
-        if l1.kpad16 != c and not self.fuse3:
             return False
         return bool(_cabi.lib().s4g_gemm_chain_supported(loader, epi, c, l1.kpad16))
 
@@ -828,7 +817,7 @@ class FusedPointNet2:
             # last FP level: the first head layer (shared input, groups == 1) rides along as a
             # third layer, so the per-point features never go through HBM before the heads
             h0 = self.head_layers[0]
-            fuse3 = (fuse2 and fi == len(self.fp) - 1 and self.fuse3 and self.heads_fused is None and
+            fuse3 = (fuse2 and fi == len(self.fp) - 1 and self.heads_fused is None and
                      fl[-1].cout == fl[-2].cout and
                      h0.groups == 1 and h0.cin == fl[-1].cout and h0.kpad16 == fl[-1].cout and
                      h0.cout % 64 == 0 and h0.Wfrag is not None)
@@ -868,13 +857,12 @@ class FusedPointNet2:
                     la, lb, _ = self._fp_split(fp, layer, c2, c1)
                     s_out = None if carried is not None else \
                         torch.empty((B * n_sparse, layer.cout), dtype=torch.float32, device=dev)
-                    # the sum is formed by the NEXT launch's loader where that is faster
-                    # (S4G_FP_LOADER_ADD = list of FP levels), else by interp_add_cl_kernel
-                    if self.fp_loader_add == "auto":
-                        in_loader = chain_next or (fuse2 and len(fl) == 3 and
-                                                   self._fusable(fl[-2], fl[-1], LOAD_INTERP_ADD, EPI_STORE))
-                    else:
-                        in_loader = self.fp_loader_add != "none" and fi in self.fp_loader_add
+                    # the interpolate + add + ReLU is formed by the NEXT launch's loader where that launch is a
+                    # fused chain, whose panel is loaded once -- the tiled kernel would repeat the gathers per
+                    # column tile: measured 0.41 ms against 0.14 + 0.18 ms at FP level 1 -- else by
+                    # interp_add_cl_kernel
+                    in_loader = chain_next or (fuse2 and len(fl) == 3 and
+                                               self._fusable(fl[-2], fl[-1], LOAD_INTERP_ADD, EPI_STORE))
                     in_loader = in_loader and self.precision in ("f16x2", "bf16") and len(fl) >= 2
                     if in_loader and fuse2 and not self._fusable(fl[-2], fl[-1], LOAD_INTERP_ADD, EPI_STORE):
                         in_loader = False
@@ -955,7 +943,7 @@ class FusedPointNet2:
             # two or three consecutive grouped layers as one launch where the widths allow it
             l2 = hl[l + 1] if (l + 1 < len(hl) and self._fusable(layer, hl[l + 1])) else None
             l3 = None
-            if (l2 is not None and self.fuse3 and l + 2 < len(hl) and l2.cout == layer.cout and
+            if (l2 is not None and l + 2 < len(hl) and l2.cout == layer.cout and
                     self._fusable(l2, hl[l + 2])):
                 l3 = hl[l + 2]
             if l2 is not None and l3 is None and layer.kpad16 != layer.cout:

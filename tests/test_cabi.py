@@ -69,27 +69,6 @@ def test_product_package_never_imports_oracle():
                 assert not re.search(r"^\s*(from|import)\s+oracle\b", src, flags=re.M), f
 
 
-def test_measurement_build_with_the_kernel_variants_compiles(tmp_path):
-    """`-DS4G_VARIANTS` (csrc/variants/*.inc: the measured-slower kernels kept for A/B runs) must keep compiling
-    against the shipped sources -- a change of a shared struct once broke it unnoticed -- and must say what it is."""
-    import ctypes
-    import shutil
-    import subprocess
-    hipcc = "/opt/rocm/bin/hipcc"
-    if not os.path.exists(hipcc):
-        pytest.skip("no hipcc on this machine")
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    lib = tmp_path / "libs4g_hip_variants.so"
-    out = subprocess.run(["make", "-C", os.path.join(root, "s4g_release_amd", "csrc"), "-j8", "OBJDIR=%s" % tmp_path,
-                          "LIB=%s" % lib, "HIPFLAGS_EXTRA=-DS4G_VARIANTS"], capture_output=True, text=True, timeout=1500)
-    assert out.returncode == 0, out.stderr[-3000:]
-    import torch  # noqa: F401  (its HIP runtime first, as _cabi.lib does)
-    h = ctypes.CDLL(str(lib))
-    from s4g_release_amd import _cabi
-    assert h.s4g_build_variants() == 1 and h.s4g_abi_version() == _cabi.S4G_ABI_VERSION
-    shutil.rmtree(tmp_path, ignore_errors=True)
-
-
 def test_ab_knobs_are_ignored_without_the_master_switch(monkeypatch):
     """include/s4g_ops.h: the A/B / test knobs are read only with S4G_TEST_KNOBS=1 (tests/conftest.py sets it).  Host side
     (`_cabi.knob`) and library side (`s4g_test_knobs_enabled`, csrc/s4g_common.h s4g::knob) agree; the production surface
@@ -104,8 +83,8 @@ def test_ab_knobs_are_ignored_without_the_master_switch(monkeypatch):
     assert _cabi.knob("S4G_GEMM_FUSE2", "1") == "1"
     L = ctypes.CDLL(_cabi.LIB_PATH)                                 # no compute call: the symbol and its answer
     L.s4g_test_knobs_enabled.restype = ctypes.c_int
-    variants = ctypes.CDLL(_cabi.LIB_PATH).s4g_build_variants()
-    assert L.s4g_test_knobs_enabled() == (1 if variants else 0)
+    assert L.s4g_build_variants() == 0                              # kept in the ABI; no library carries variants
+    assert L.s4g_test_knobs_enabled() == 0
     monkeypatch.setenv("S4G_TEST_KNOBS", "1")
     assert L.s4g_test_knobs_enabled() == 1
     # every direct environment read in the package is one of the production variables (or torch.distributed's own)
@@ -123,3 +102,33 @@ def test_ab_knobs_are_ignored_without_the_master_switch(monkeypatch):
             src = open(os.path.join(csrc, f)).read()
             direct = re.findall(r'(?<![:\w])getenv\("([A-Z0-9_]+)"\)', src)
             assert set(direct) <= {"S4G_TEST_KNOBS"}, (f, direct)
+
+
+def test_knob_table_lists_exactly_the_knobs_that_are_read_and_tested():
+    """The A/B list of include/s4g_ops.h is the set of knobs the code reads (`_cabi.knob("NAME"` in the package,
+    `s4g::knob("NAME")` in csrc/), and every one of them is set by at least one test: a knob nothing drives is dead
+    code and goes, together with the path it selects."""
+    header = open(os.path.join(ROOT, "include", "s4g_ops.h")).read()
+    table = header[header.index("A/B AND TEST KNOBS"):]
+    table = table[:table.index("*/")]
+    listed = set(re.findall(r"\bS4G_[A-Z0-9_]+", table)) - {"S4G_TEST_KNOBS"}
+    assert listed, "the knob table of include/s4g_ops.h was not found"
+    pkg = os.path.join(ROOT, "s4g_release_amd")
+    read = set()
+    for f in sorted(os.listdir(pkg)):
+        if f.endswith(".py"):
+            read |= set(re.findall(r'_cabi\.knob\(\s*"(S4G_[A-Z0-9_]+)"', open(os.path.join(pkg, f)).read()))
+    csrc = os.path.join(pkg, "csrc")
+    for dirpath, _, files in os.walk(csrc):
+        for f in sorted(files):
+            if f.endswith((".hip", ".h", ".inc")):
+                read |= set(re.findall(r'(?<![\w.])(?:s4g::)?knob\(\s*"(S4G_[A-Z0-9_]+)"\s*\)',
+                                       open(os.path.join(dirpath, f)).read()))
+    assert read == listed, (sorted(read - listed), sorted(listed - read))
+    tests_dir = os.path.join(ROOT, "tests")
+    driven = set()
+    for dirpath, _, files in os.walk(tests_dir):
+        for f in sorted(files):
+            if f.endswith(".py"):
+                driven |= set(re.findall(r'setenv\(\s*"(S4G_[A-Z0-9_]+)"', open(os.path.join(dirpath, f)).read()))
+    assert listed <= driven, sorted(listed - driven)

@@ -11,7 +11,6 @@ import pytest
 import torch
 
 from tests import golden_util as GU
-from tests.conftest import with_variants
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-4
@@ -19,17 +18,12 @@ TOL = 1e-4
 FUZZ_SEEDS = int(os.environ.get("S4G_FUZZ_SEEDS", "6"))
 
 
-@pytest.fixture(params=with_variants(["chain", "tiled"], ["resident"]))
+@pytest.fixture(params=["chain", "tiled"])
 def gemm_variant(request, monkeypatch):
     """Unit tests run per single-layer kernel: default dispatch (plain layers whose widths allow it on the
-    chain kernel's first-layer machinery), the tiled kernel for every shape (S4G_GEMM_SINGLE_CHAIN=0) and --
-    measurement builds only -- the resident-A kernel forced wherever it applies (S4G_GEMM_RESIDENT=1)."""
-    if request.param == "resident":
+    chain kernel's first-layer machinery) and the tiled kernel for every shape (S4G_GEMM_SINGLE_CHAIN=0)."""
+    if request.param == "tiled":
         monkeypatch.setenv("S4G_GEMM_SINGLE_CHAIN", "0")
-        monkeypatch.setenv("S4G_GEMM_RESIDENT", "1")
-    elif request.param == "tiled":
-        monkeypatch.setenv("S4G_GEMM_SINGLE_CHAIN", "0")
-        monkeypatch.setenv("S4G_GEMM_RESIDENT", "0")
     else:
         monkeypatch.setenv("S4G_GEMM_SINGLE_CHAIN", "1")     # every shape the chain form supports, not only where it wins
     return request.param
@@ -74,7 +68,7 @@ def _h2(w, *tensors, floor=0.0):
     planes, inv = split_f16x2(w16)
     kw = dict(W_f16x2=planes, w_inv_scale=inv, a_amax_floor=float(floor),
               out_amax=torch.zeros(64, device=w.device))
-    if w.shape[-2] % 32 == 0:     # enables the resident-A kernel where the shape qualifies
+    if w.shape[-2] % 32 == 0:     # enables the chain kernel's single-layer form where the shape qualifies
         p4 = planes if planes.dim() == 4 else planes.unsqueeze(1)
         kw["W_f16x2_frag"] = fragment_order(p4)
     for name, t in zip(("a_amax", "a_amax2"), [t for t in tensors if t is not None]):
@@ -101,7 +95,7 @@ def _padk(w):
 @pytest.mark.parametrize("P,Cin,Cout,relu", [(128, 32, 128, True), (1000, 128, 256, True),
                                              (77, 260, 21, False), (4096, 1536, 1024, True),
                                              (300, 8, 130, True),
-                                             # resident-A kernel shapes (K % 64 == 0, Cout % 128 == 0)
+                                             # shapes with the A panel resident in LDS (K % 64 == 0, Cout % 128 == 0)
                                              (777, 256, 512, True), (300, 128, 128, False),
                                              (4100, 64, 256, True), (64, 256, 2048, True)])
 @pytest.mark.parametrize("prec", PRECISIONS)
@@ -133,8 +127,6 @@ def test_gemm_two_output_tensors(dev, P, Cin, split, Cout, prec, gemm_variant):
     every output channel bit-identical to the two separate launches of the same kernel, and the per-scene
     maxima of each tensor in its own row."""
     from s4g_release_amd.fused import fragment_order, split_bf16x3
-    if gemm_variant == "resident":
-        pytest.skip("the resident-A measurement kernel has one output tensor")
     g = torch.Generator(device="cpu").manual_seed(P + Cout)
     A = torch.randn(P, Cin, generator=g).to(dev)
     W = (torch.randn(Cout, Cin, generator=g) / Cin ** 0.5).to(dev)

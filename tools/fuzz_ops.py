@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Time-boxed randomized parity sweep of the geometry operators against the CPU oracle
-(bit-exact), at sizes around every dispatch threshold: FPS register / pruned / hybrid /
-streaming kernels, ball query scan / grid / cell, 3-NN scan / grid.  Not part of the test
+(bit-exact), at sizes around every dispatch threshold: FPS register / pruned /
+streaming kernels, ball query scan / grid, 3-NN scan / grid.  Not part of the test
 suite (needs minutes); usage on a GPU box:
     python tools/fuzz_ops.py [--seconds 240] [--seed 0]
 Prints one line per case and exits non-zero at the first mismatch."""
@@ -38,7 +38,7 @@ def main():
         K = int(rng.choice([1, 5, 16, 64, 65, 128]))
         radius = float(rng.choice([0.005, 0.02, 0.05, 0.2, 1.5]))
         fps_mode = str(rng.choice(["", "dense", "pruned"]))
-        bq_mode = str(rng.choice(["", "grid", "cell", "scan"]))
+        bq_mode = str(rng.choice(["", "grid", "scan"]))
         fmad = bool(rng.integers(4) == 0)
         os.environ["S4G_TEST_KNOBS"] = "1"      # the kernel-selection knobs are ignored without the master switch
         for k, v in (("S4G_FPS_MODE", fps_mode), ("S4G_BQ_MODE", bq_mode)):
