@@ -66,7 +66,9 @@ enum { LOAD_PLAIN = 0, LOAD_GATHER = 1, LOAD_INTERP = 2, LOAD_GATHER_MLP1 = 3, L
        LOAD_INTERP_ADD = 5, LOAD_CHANNEL_FIRST = 6,
        // internal (never in a descriptor): GATHER_MLP1 on pre-gathered rel_xyz4 records in the f16x2 chain kernel --
        // the 3 -> C first layer runs on the matrix cores too (mlp_chain_kernel, "phase 0")
-       LOAD_REL_MLP1 = 64 };
+       LOAD_REL_MLP1 = 64,
+       // internal: GATHER_ADD in the f16x2 chain kernel with the xyz term on the matrix cores and the gather a plain copy
+       LOAD_ADD_MFMA0 = 65 };
 enum { EPI_STORE = 0, EPI_MAX = 1, EPI_CHANNEL_FIRST = 2, EPI_MAX_CF = 3 };
 
 struct GemmParams {
@@ -84,6 +86,7 @@ struct GemmParams {
   const float* xyz;
   const float* ctr;
   int Cf, N, M, K;
+  int nscenes;   // scenes the grouped rows span (ceil(P / (M K))): sizes the buffer resources of the LOAD_ADD_MFMA0 form
   // GATHER_MLP1: first SA layer (xyz only) evaluated in the loader:
   // A[p][k] = relu(w1[k].x*rx + w1[k].y*ry + w1[k].z*rz + w1[k].w), k < Cin
   const float4* mlp1;
@@ -1165,9 +1168,12 @@ __global__ __launch_bounds__(RW == 8 ? 512 : 256, (PL == 1 && RW != 8 && S4G_CHA
   const int lane = t & 63;
   const int wave = t >> 6;
 
-  constexpr bool ADD_BOUNDS = LOADER == LOAD_GATHER_ADD || LOADER == LOAD_INTERP_ADD;   // the loader SUMS its inputs
+  // GATHER_ADD with its vector work on the matrix cores: the gather is a copy into LDS, the xyz term one MFMA step
+  constexpr bool ADD0 = LOADER == LOAD_ADD_MFMA0;
+  constexpr bool ADD_BOUNDS = LOADER == LOAD_GATHER_ADD || LOADER == LOAD_INTERP_ADD || ADD0;   // the loader SUMS its inputs
   constexpr bool MFMA0 = LOADER == LOAD_REL_MLP1;   // the xyz-only first layer as one 16-deep MFMA step (f16x2 form only)
-  static_assert(!MFMA0 || (PL == 2 && KC == 1), "phase 0 on the matrix cores: f16x2, one panel");
+  static_assert(!(MFMA0 || ADD0) || (PL == 2 && KC == 1), "phase 0 on the matrix cores: f16x2, one panel");
+  static_assert(!ADD0 || EPI2 == EPI_MAX, "a wave's 64 rows are one centroid's neighbours");
   constexpr bool SEGMAX = (LOADER == LOAD_GATHER_MLP1 || MFMA0) && EPI2 == EPI_MAX;   // may run on distinct rows only (seg4)
   const int tile = blockIdx.x;
   const int p0 = tile * BM;
@@ -1232,7 +1238,82 @@ __global__ __launch_bounds__(RW == 8 ? 512 : 256, (PL == 1 && RW != 8 && S4G_CHA
   // layer, requested before anything waits (buffer loads: a row past P reads zeros)
   float4 rv0[NRB];
   float4 wv0 = f4zero();
-  if constexpr (MFMA0) {
+  // ADD0: the thread's 16-byte pieces of the gathered F rows (row t / 8 + RS s, columns 32 kt + 4 (t % 8) ..), in
+  // flight from here to the staging store behind the MFMA step
+  constexpr int NKT0 = ADD0 ? K / 32 : 1, RPT0 = ADD0 ? RPT : 1;
+  float4 fa[NKT0][RPT0];
+  constexpr int fstr = K + 4;   // fp32 staging row stride (floats), see the accumulate step
+  if constexpr (ADD0) {
+    // A = relu(F[b N + gidx] + w1 . (xyz_j - ctr_m, 1)).  The dispatch guarantees K == 64 neighbours and P % 64 == 0,
+    // so every 64-row group of the tile -- a wave's rows -- is ONE centroid: scene, centroid and "past P" are
+    // wave-uniform scalars.  Everything a row needs comes through buffer resources (scalar base, 32-bit offsets:
+    // the dispatch checks the tensors fit; a read past the records returns zeros -- rows past P, channels past Cin).
+    const int rows_left = p.P - p0;
+    const __amdgpu_buffer_rsrc_t ridx = __builtin_amdgcn_make_buffer_rsrc(
+        const_cast<int*>(p.gidx + p0), 0, (rows_left < BM ? rows_left : BM) * 4, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rxyz = __builtin_amdgcn_make_buffer_rsrc(
+        const_cast<float*>(p.xyz), 0, p.nscenes * 3 * p.N * 4, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rfeat = __builtin_amdgcn_make_buffer_rsrc(
+        const_cast<float*>(p.feat), 0, p.nscenes * p.N * p.Cf * 4, 0x00020000);
+    constexpr uint32_t OOB = 0x80000000u;   // past every resource above (each is < 2^31 bytes)
+    // all index loads first: the rows of this lane's position operand, then the rows this thread copies
+    int jr[NRB], jg[RPT];
+#pragma unroll
+    for (int rb = 0; rb < NRB; ++rb)
+      jr[rb] = __builtin_amdgcn_raw_buffer_load_b32(ridx, (wr * WROWS + rb * 32 + li) * 4, 0, 0);
+#pragma unroll
+    for (int s = 0; s < RPT; ++s) jg[s] = __builtin_amdgcn_raw_buffer_load_b32(ridx, ((t >> 3) + RS * s) * 4, 0, 0);
+    // the wave's centroid and its (rel, 0) records: the same single rounded subtraction as the vector-ALU loader
+    {
+      int bw, mw;
+      gather_row_bm(p.M, p.K, p0, __builtin_amdgcn_readfirstlane(wr * WROWS), bw, mw);
+      bw = __builtin_amdgcn_readfirstlane(bw);
+      mw = __builtin_amdgcn_readfirstlane(mw);
+      const bool okw = p0 + wr * WROWS < p.P;
+      float cx = 0.f, cy = 0.f, cz = 0.f;
+      if (okw) {
+        const float* c = p.ctr + (size_t)bw * 3 * p.M + mw;
+        cx = c[0];
+        cy = c[p.M];
+        cz = c[2 * p.M];
+      }
+      const uint32_t xb = okw ? (uint32_t)(bw * 3 * p.N) * 4u : OOB;
+#pragma unroll
+      for (int rb = 0; rb < NRB; ++rb) {
+        const uint32_t vo = xb + (uint32_t)jr[rb] * 4u;
+        const float x = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rxyz, vo, 0, 0));
+        const float y = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rxyz, vo + (uint32_t)p.N * 4u, 0, 0));
+        const float z = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rxyz, vo + (uint32_t)p.N * 8u, 0, 0));
+        rv0[rb] = make_float4(__fsub_rn(x, cx), __fsub_rn(y, cy), __fsub_rn(z, cz), 0.f);
+      }
+    }
+    // the gather: 8 lanes per row, 16 bytes per lane, the whole panel in flight; nothing is computed on the way
+    uint32_t rowoff[RPT];
+#pragma unroll
+    for (int s = 0; s < RPT; ++s) {
+      const int c64 = (RS * s) / 64 * 64;   // the 64-row group of row t / 8 + RS s (t / 8 < RS, and RS divides 64 or is it)
+      int bc, mc;
+      gather_row_bm(p.M, p.K, p0, c64, bc, mc);
+      bc = __builtin_amdgcn_readfirstlane(bc);
+      rowoff[s] = p0 + c64 < p.P ? (uint32_t)((bc * p.N + jg[s]) * p.Cf + (t & 7) * 4) * 4u : OOB;
+    }
+    if (p.Cin >= K) {
+#pragma unroll
+      for (int kt = 0; kt < NKT0; ++kt)
+#pragma unroll
+        for (int s = 0; s < RPT; ++s)
+          fa[kt][s] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rfeat, rowoff[s] + kt * 128, 0, 0));
+    } else {   // channels past Cin stay zero
+#pragma unroll
+      for (int kt = 0; kt < NKT0; ++kt)
+#pragma unroll
+        for (int s = 0; s < RPT; ++s)
+          fa[kt][s] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(
+                                                     rfeat, kt * 32 + (t & 7) * 4 < p.Cin ? rowoff[s] + kt * 128 : OOB, 0, 0));
+    }
+    const int ch = wc * 64 + lane;
+    if (ch < p.Cin) wv0 = p.mlp1[ch];
+  } else if constexpr (MFMA0) {
     const int rows_left = p.P - p0;
     const __amdgpu_buffer_rsrc_t rrel = __builtin_amdgcn_make_buffer_rsrc(
         const_cast<float4*>(p.rel4 + p0), 0, (rows_left < BM ? rows_left : BM) * 16, 0x00020000);
@@ -1299,7 +1380,7 @@ __global__ __launch_bounds__(RW == 8 ? 512 : 256, (PL == 1 && RW != 8 && S4G_CHA
   const uint16_t* a_lane = Ah + (wr * WROWS + li) * astr + 8 * lh;
   float* epi_s = scr + wave * 128;
   f32x16 acc[2][NRB];   // [32-channel block][32-row block], in every phase
-  if constexpr (MFMA0) {
+  if constexpr (MFMA0 || ADD0) {
     // ---- phase 0: H0 = relu(W1 (rel, 1)) for this wave's WROWS rows x 64 channels as ONE 16-deep step of the
     // f16x2 contraction (12 MFMAs) instead of 3 FMAs + ReLU + select per element on the vector ALU.
     //   position operand: lane (li, lh) holds (rx, ry, rz, ONE) s_a at k = 8 lh .. 8 lh + 3 -- BOTH half-waves carry
@@ -1309,6 +1390,7 @@ __global__ __launch_bounds__(RW == 8 ? 512 : 256, (PL == 1 && RW != 8 && S4G_CHA
     //     half's k slots and zeros in the other block's, so block cb's fragment is "mine where lh == cb, else 0" --
     //     no lane exchange; s_w = the channel's own power-of-two scale (its largest entry in [2^14, 2^15))
     // acc = s_a s_w (w . rel + b); the epilogue applies relu, then splits with f = sa / (s_a s_w) per channel.
+    // (ADD0: the epilogue first forms F + acc / (s_a s_w) -- see there.)
     float m = 0.f;
 #pragma unroll
     for (int rb = 0; rb < NRB; ++rb)
@@ -1323,7 +1405,7 @@ __global__ __launch_bounds__(RW == 8 ? 512 : 256, (PL == 1 && RW != 8 && S4G_CHA
     uint32_t ew = __float_as_uint(mw) >> 23;
     ew = ew < 15u ? 15u : (ew > 240u ? 240u : ew);
     const float s_w = __uint_as_float((268u - ew) << 23);
-    epi_s[lane] = __uint_as_float((ew - 14u) << 23) * inv_a * sa;
+    epi_s[lane] = __uint_as_float((ew - 14u) << 23) * inv_a * (ADD0 ? 1.f : sa);
     uint32_t wh01, wl01, wh23, wl23;
     split_quad_h(wv0.x, wv0.y, wv0.z, bq, s_w, wh01, wl01, wh23, wl23);
     uint4 af0[NRB][2], bf0[2][2];
@@ -1362,22 +1444,72 @@ __global__ __launch_bounds__(RW == 8 ? 512 : 256, (PL == 1 && RW != 8 && S4G_CHA
         acc[cb][rb] = chain_mfma<PL>(bf0[cb][0], af0[rb][1], acc[cb][rb]);
         acc[cb][rb] = chain_mfma<PL>(bf0[cb][0], af0[rb][0], acc[cb][rb]);
       }
+    if constexpr (ADD0) {
+      // The two fp16 planes [2][BM][K + 8] are exactly the bytes of an fp32 panel [BM][K + 8]: the gathered rows are
+      // staged in the panel's own space as raw fp32 -- register staging, because an LDS-DMA piece lands as 1 KiB of
+      // CONTIGUOUS LDS (8 rows x 128 B at a 32-dword row stride), which the accumulator-layout read below would hit
+      // 8-way; a padded row stride needs the store address per lane.  ds_write_b128 is serviced 8 lanes at a time on
+      // 32 banks: a row's eight lanes cover 32 consecutive dwords, free at any stride.
+      float* Fs = smemf;
 #pragma unroll
-    for (int nb = 0; nb < 2; ++nb)
+      for (int kt = 0; kt < NKT0; ++kt)
 #pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const float4 f4 = *reinterpret_cast<const float4*>(epi_s + nb * 32 + 8 * j + 4 * lh);
+        for (int s = 0; s < RPT; ++s)
+          *reinterpret_cast<float4*>(Fs + ((t >> 3) + RS * s) * fstr + kt * 32 + (t & 7) * 4) = fa[kt][s];
+      __syncthreads();
+      // acc = F + (w . rel + b): lane (li, lh) holds, of row li, channels 32 nb + 8 j + 4 lh + (0..3) in registers
+      // 4 j .. 4 j + 3 -- one ds_read_b128 at dword li fstr + 4 lh + const.  A b128 read is serviced in four groups of 16
+      // lanes ({0-3, 12-15, 20-27} and {4-11, 16-19, 28-31} of each half-wave) on 64 banks: with fstr = K + 4 = 4 (mod 64)
+      // lane li starts at bank 4 (li mod 16) (+ 4 lh), and each group's li mod 16 are the 16 distinct values, so its
+      // 16 x 4 dwords are the 64 banks once: conflict-free (K + 8 would put li and li + 8 on the same banks).
+      // acc / (s_a s_w) is exact (a power of two), so the FMA is the ONE rounded fp32 add of the vector-ALU loader.
 #pragma unroll
-        for (int pb = 0; pb < NRB; ++pb) {
-          uint16_t* dst = Ah + (wr * WROWS + pb * 32 + li) * astr + wc * 64 + nb * 32 + 8 * j + 4 * lh;
-          uint2 h, l;
-          split_quad_h2(fmaxf(acc[nb][pb][4 * j], 0.f), fmaxf(acc[nb][pb][4 * j + 1], 0.f),
-                        fmaxf(acc[nb][pb][4 * j + 2], 0.f), fmaxf(acc[nb][pb][4 * j + 3], 0.f), f4.x, f4.y, f4.z, f4.w,
-                        h.x, l.x, h.y, l.y);
-          *reinterpret_cast<uint2*>(dst) = h;
-          *reinterpret_cast<uint2*>(dst + aplane) = l;
+      for (int nb = 0; nb < 2; ++nb)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const float4 f4 = *reinterpret_cast<const float4*>(epi_s + nb * 32 + 8 * j + 4 * lh);
+#pragma unroll
+          for (int pb = 0; pb < NRB; ++pb) {
+            const float4 fv = *reinterpret_cast<const float4*>(Fs + (wr * WROWS + pb * 32 + li) * fstr + wc * 64 + nb * 32 +
+                                                               8 * j + 4 * lh);
+            acc[nb][pb][4 * j] = __fmaf_rn(acc[nb][pb][4 * j], f4.x, fv.x);
+            acc[nb][pb][4 * j + 1] = __fmaf_rn(acc[nb][pb][4 * j + 1], f4.y, fv.y);
+            acc[nb][pb][4 * j + 2] = __fmaf_rn(acc[nb][pb][4 * j + 2], f4.z, fv.z);
+            acc[nb][pb][4 * j + 3] = __fmaf_rn(acc[nb][pb][4 * j + 3], f4.w, fv.w);
+          }
         }
-      }
+      __syncthreads();   // every wave has read its F values: the planes may now overwrite the staging
+#pragma unroll
+      for (int nb = 0; nb < 2; ++nb)
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+#pragma unroll
+          for (int pb = 0; pb < NRB; ++pb) {
+            uint16_t* dst = Ah + (wr * WROWS + pb * 32 + li) * astr + wc * 64 + nb * 32 + 8 * j + 4 * lh;
+            uint2 h, l;
+            split_quad_h(fmaxf(acc[nb][pb][4 * j], 0.f), fmaxf(acc[nb][pb][4 * j + 1], 0.f),
+                         fmaxf(acc[nb][pb][4 * j + 2], 0.f), fmaxf(acc[nb][pb][4 * j + 3], 0.f), sa, h.x, l.x, h.y, l.y);
+            *reinterpret_cast<uint2*>(dst) = h;
+            *reinterpret_cast<uint2*>(dst + aplane) = l;
+          }
+    } else {
+#pragma unroll
+      for (int nb = 0; nb < 2; ++nb)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const float4 f4 = *reinterpret_cast<const float4*>(epi_s + nb * 32 + 8 * j + 4 * lh);
+#pragma unroll
+          for (int pb = 0; pb < NRB; ++pb) {
+            uint16_t* dst = Ah + (wr * WROWS + pb * 32 + li) * astr + wc * 64 + nb * 32 + 8 * j + 4 * lh;
+            uint2 h, l;
+            split_quad_h2(fmaxf(acc[nb][pb][4 * j], 0.f), fmaxf(acc[nb][pb][4 * j + 1], 0.f),
+                          fmaxf(acc[nb][pb][4 * j + 2], 0.f), fmaxf(acc[nb][pb][4 * j + 3], 0.f), f4.x, f4.y, f4.z, f4.w,
+                          h.x, l.x, h.y, l.y);
+            *reinterpret_cast<uint2*>(dst) = h;
+            *reinterpret_cast<uint2*>(dst + aplane) = l;
+          }
+        }
+    }
   } else {
     if (!(S4G_CHAIN_ABLATE & 16)) load_panel(0, std::integral_constant<int, (K / 32) / (NRB / 2)>{});
   }
@@ -1912,6 +2044,7 @@ extern "C" int s4g_mlp_gemm_f32(const s4g_gemm_desc_t* d, s4g_stream_t stream) {
   p.A = d->A; p.lda = d->lda; p.a_coff = d->a_coff; p.a_gcol = d->a_gcol; p.aL = d->a_L;
   p.gidx = d->gidx; p.feat = d->feat; p.xyz = d->xyz; p.ctr = d->ctr;
   p.Cf = d->Cf; p.N = d->N; p.M = d->M; p.K = d->K;
+  p.nscenes = d->M > 0 && d->K > 0 ? (int)((d->P + (int64_t)d->M * d->K - 1) / ((int64_t)d->M * d->K)) : 0;
   p.mlp1 = (const float4*)d->mlp1_w;
   p.rel4 = (const float4*)d->rel_xyz4;
   p.seg4 = d->seg4;
@@ -2039,6 +2172,13 @@ extern "C" int s4g_mlp_gemm_f32(const s4g_gemm_desc_t* d, s4g_stream_t stream) {
         return c128 ? launch_mlp_chain<LOAD_REL_MLP1, EPI_MAX, 2, 1, 2>(p, d->groups, st)
                     : launch_mlp_chain<LOAD_REL_MLP1, EPI_MAX, 1, 1, 2>(p, d->groups, st);
     }
+    // GATHER_ADD pairs of the f16x2 form: the gather as a copy, the xyz term as one MFMA step (mlp_chain_kernel, ADD0).
+    // Its buffer resources take 32-bit byte offsets; a tensor past 2 GiB keeps the vector-ALU loader below.
+    if (h2 && d->loader == S4G_GEMM_LOAD_GATHER_ADD && d->epilogue == S4G_GEMM_EPI_MAX && d->Kpad16 == d->Cout &&
+        (int64_t)p.nscenes * d->N * d->Cf * 4 < (1ll << 31) && (int64_t)p.nscenes * d->N * 12 < (1ll << 31))
+      return c128   ? launch_mlp_chain<LOAD_ADD_MFMA0, EPI_MAX, 2, 1, 2>(p, d->groups, st)
+             : c256 ? launch_mlp_chain<LOAD_ADD_MFMA0, EPI_MAX, 1, 1, 2>(p, d->groups, st)
+                    : launch_mlp_chain<LOAD_ADD_MFMA0, EPI_MAX, 8, 1, 2>(p, d->groups, st);
 #define S4G_FUSED2_CASE(L, E, R, KCH)                                                        \
   if (d->loader == L && (int)d->epilogue == (int)E && (c128 ? 2 : (c256 ? 1 : 8)) == R &&     \
       d->Kpad16 / d->Cout == KCH)                                                             \
