@@ -58,7 +58,9 @@ extern "C" {
  * 13: s4g_contact_heads_f32 (output tail of the contact network, MODEL.TYPE "PN2"), s4g_decode_poses_abs_f32
  *     (pose decode for an absolute translation head); no layout change.
  * 14: S4G_GEMM_LOAD_CHANNEL_FIRST, S4G_GEMM_EPI_MAX_CHANNEL_FIRST and s4g_gemm_desc_t.a_L (any SharedMLP / SA max-pool
- *     on its own (B, C, L) tensors: s4g_release_amd.accelerate), s4g_amax_per_scene_f32. */
+ *     on its own (B, C, L) tensors: s4g_release_amd.accelerate), s4g_amax_per_scene_f32.
+ *     Added under 14 with no layout change: s4g_eval_frames_f32 / s4g_eval_frames_workspace_bytes (batched antipodal
+ *     and collision grading of grasp frames against a labelled scene cloud with normals). */
 #define S4G_ABI_VERSION 14
 
 /* ---------------------------------------------------------------------------
@@ -689,6 +691,32 @@ int s4g_collision_counts_f32(const float *xyz_b3n, const float *g2l_bk44, int64_
 int s4g_collision_counts_n_f32(const float *xyz_b3n, const float *g2l_bk44, int64_t B, int64_t N,
                                int64_t K, const float *gripper6, const int64_t *pose_count_b,
                                int invert_se3, int32_t *counts_bk2, s4g_stream_t stream);
+
+/* Grading of grasp frames against the dense, labelled scene cloud (csrc/eval_frames.hip): EvalExpCloud.eval_frame
+ * (eval_experiment/eval_point_cloud.py:39-113) for every pose of every scene, without host synchronisation.
+ * xyz, normals (B, 3, N) fp32 (the normals are rotated by g2l[:3, :3] and NOT re-normalised), labels (B, N) int32,
+ * g2l (B, K, 4, 4), pose_count_b and invert_se3 as in s4g_collision_counts_n_f32.  params10 (HOST pointer) = the six
+ * values of gripper6, then {BACK_COLLISION_THRESHOLD, FINGER_COLLISION_THRESHOLD, CLOSE_REGION_MIN_POINTS,
+ * NEIGHBOR_DEPTH} (eval_experiment/config.py:39-48).  Every inequality is strict, all arithmetic fp32.
+ * Outputs, per pose row:
+ *   ints_bk8   int32 (B, K, 8) = {back, finger, close, multi_objects, n_left, n_right, collision, 0}: back / finger are
+ *              the two integers of s4g_collision_counts_n_f32 bit for bit; close = points of the close region (:95-97);
+ *              multi_objects = more than one distinct label among them; collision = back > params[6] or finger >
+ *              params[7]; n_left / n_right = populations of the two bands of _antipodal_score (:56-57)
+ *   floats_bk5 fp32 (B, K, 5) = {left_y, right_y, mean_left, mean_right, score}: left_y / right_y = maximum / minimum
+ *              of local y over the close region (0 when it is empty); mean_* = mean |n_local.y| over the band;
+ *              score = mean_left * mean_right.
+ *   n_left, n_right, mean_left, mean_right and score are 0 unless the pose reaches the score: close >= params[8],
+ *   no collision, one label (:107-111).  Rows at or past pose_count_b[b] are not scanned and read 0 everywhere.
+ * Run-to-run bit-identical: integers and extrema by integer atomics, the band sums in a fixed order (per-chunk
+ * partials in the workspace, summed pairwise in chunk order), no floating-point atomics.
+ * N < 2^30 (S4G_EINVAL otherwise).
+ * Workspace: s4g_eval_frames_workspace_bytes(B, N, K) bytes, 256-byte aligned; contents need not be initialised. */
+size_t s4g_eval_frames_workspace_bytes(int64_t B, int64_t N, int64_t K);
+int s4g_eval_frames_f32(const float *xyz_b3n, const float *normals_b3n, const int32_t *labels_bn,
+                        const float *g2l_bk44, int64_t B, int64_t N, int64_t K, const float *params10,
+                        const int64_t *pose_count_b, int invert_se3, int32_t *ints_bk8, float *floats_bk5,
+                        void *workspace, size_t workspace_bytes, s4g_stream_t stream);
 
 /* ---- next row f3: cloud pre-processing on device -------------------------
  * Single-scene passes in front of the network (reference

@@ -156,11 +156,6 @@ extern "C" int s4g_decode_poses_abs_f32(const float* frame_R_b9n, const float* f
 // ---------------------------------------------------------------------------
 namespace s4g {
 
-struct GripperBox {
-  float finger_length, bottom_length, half_hand_thickness, half_bottom_width, half_bottom_space,
-      back_margin;
-};
-
 constexpr int COLL_CHUNKS = 8;     // point ranges per scene (a workgroup scans one range)
 constexpr int COLL_GX = 16;        // workgroups that share a scene's pose list (pose k belongs to workgroup k mod 16)
 constexpr int COLL_U = 4;          // points per lane held in registers while the workgroup's poses pass over them
@@ -191,25 +186,7 @@ __global__ __launch_bounds__(256) void collision_counts_kernel(
       const int k = blockIdx.x + COLL_GX * (j0 + t);
       cnt[t][0] = cnt[t][1] = 0;
       if (k < kmax) {
-        const float* G = g2l + ((size_t)b * K + k) * 16;   // row-major 4x4
-        float g00 = G[0], g01 = G[1], g02 = G[2], g03 = G[3];
-        float g10 = G[4], g11 = G[5], g12 = G[6], g13 = G[7];
-        float g20 = G[8], g21 = G[9], g22 = G[10], g23 = G[11];
-        if (invert_se3) {
-          // the matrix is the POSE (gripper -> global): its analytic SE(3) inverse [R^T | -R^T t] in fp32
-          // (torch_batch_transformation_inv, utils/math_utils.py:26-40, as grasp_detector.py:219 calls it) -- formed
-          // here instead of by a batched 3x3 library GEMM per call (0.26 ms for 16 x 2 048 poses)
-          const float tx = g03, ty = g13, tz = g23;
-          const float r01 = g01, r02 = g02, r12 = g12;
-          g01 = g10; g02 = g20; g12 = g21;
-          g10 = r01; g20 = r02; g21 = r12;
-          g03 = -__fadd_rn(__fadd_rn(__fmul_rn(g00, tx), __fmul_rn(g01, ty)), __fmul_rn(g02, tz));
-          g13 = -__fadd_rn(__fadd_rn(__fmul_rn(g10, tx), __fmul_rn(g11, ty)), __fmul_rn(g12, tz));
-          g23 = -__fadd_rn(__fadd_rn(__fmul_rn(g20, tx), __fmul_rn(g21, ty)), __fmul_rn(g22, tz));
-        }
-        gl[t][0] = g00; gl[t][1] = g01; gl[t][2] = g02; gl[t][3] = g03;
-        gl[t][4] = g10; gl[t][5] = g11; gl[t][6] = g12; gl[t][7] = g13;
-        gl[t][8] = g20; gl[t][9] = g21; gl[t][10] = g22; gl[t][11] = g23;
+        load_g2l(g2l + ((size_t)b * K + k) * 16, invert_se3, gl[t]);   // row-major 4x4 (s4g_common.h)
       }
     }
     __syncthreads();
@@ -228,24 +205,15 @@ __global__ __launch_bounds__(256) void collision_counts_kernel(
         z[u] = px[2 * (size_t)N + ii];
       }
       for (int sl = 0; sl < nslot; ++sl) {
-        const float g00 = gl[sl][0], g01 = gl[sl][1], g02 = gl[sl][2], g03 = gl[sl][3];
-        const float g10 = gl[sl][4], g11 = gl[sl][5], g12 = gl[sl][6], g13 = gl[sl][7];
-        const float g20 = gl[sl][8], g21 = gl[sl][9], g22 = gl[sl][10], g23 = gl[sl][11];
+        float gm[12];
+#pragma unroll
+        for (int c = 0; c < 12; ++c) gm[c] = gl[sl][c];
         int nback = 0, nfing = 0;
 #pragma unroll
         for (int u = 0; u < COLL_U; ++u) {
-          const float lx = g00 * x[u] + g01 * y[u] + g02 * z[u] + g03;
-          const float ly = g10 * x[u] + g11 * y[u] + g12 * z[u] + g13;
-          const float lz = g20 * x[u] + g21 * y[u] + g22 * z[u] + g23;
-          const bool close = (lx < g.finger_length) && (lx > -g.bottom_length);            // :39-40
-          const bool zin = (lz < g.half_hand_thickness) && (lz > -g.half_hand_thickness);  // :44-45
-          const bool back = in[u] && close && zin && (ly < g.half_bottom_width) && (ly > -g.half_bottom_width) &&
-                            (lx < -g.back_margin);                                          // :47-49
-          const bool fl = (ly < g.half_bottom_width) && (ly > g.half_bottom_space);        // :54-55
-          const bool fr = (ly > -g.half_bottom_width) && (ly < -g.half_bottom_space);      // :56-57
-          const bool fing = in[u] && close && zin && (fl || fr);                            // :59-60
-          nback += __popcll(__ballot(back));      // wave-uniform
-          nfing += __popcll(__ballot(fing));
+          const GripperRegions r = gripper_regions(gm, x[u], y[u], z[u], g);
+          nback += __popcll(__ballot(in[u] && r.back));      // wave-uniform
+          nfing += __popcll(__ballot(in[u] && r.fing));
         }
         if (lane == 0) {
           if (nback) atomicAdd(&cnt[sl][0], nback);

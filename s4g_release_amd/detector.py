@@ -206,6 +206,19 @@ class GraspDetector:
         n = int(out[2][0])
         return out[0][0, :n], out[1][0, :n]
 
+    def evaluate(self, out, scene_points, scene_normals, scene_labels):
+        """Grade a `detect_device` / `submit(...).result()` result against the labelled scene cloud
+        (`EvalExpCloud.eval_frame`, eval_experiment/eval_point_cloud.py:64-113; the caller's loop over the proposed
+        frames, utils/file_logger_cls.py:223-230, in one call): scene_points, scene_normals (B, 3, N) fp32 in the frame
+        of the returned poses, scene_labels (B, N) int32 -> (candidates, selected), two
+        `postprocess.FrameEvaluation`s over `out.candidates` (its device-side count decides which rows are poses) and
+        over the selected poses.  The analytic SE(3) inverse, as in the collision check; nothing waits for the device."""
+        H, _, _, count = out.candidates
+        cand = _post.eval_frames(H, scene_points, scene_normals, scene_labels, self.gripper, inverse="se3", count=count)
+        sel = _post.eval_frames(out[0], scene_points, scene_normals, scene_labels, self.gripper, inverse="se3",
+                                count=out[2])
+        return cand, sel
+
     def stage_ms(self):
         """Milliseconds per stage of the last `detect_device` call when `stage_events` was a list (synchronises)."""
         torch.cuda.synchronize()

@@ -326,6 +326,8 @@ class GripperConfig:
     back_collision_margin: float = 0.0
     back_collision_threshold: float = 10 * math.sqrt(8)
     finger_collision_threshold: float = 10
+    close_region_min_points: float = 50         # eval_experiment/config.py:43
+    neighbor_depth: float = 0.005               # eval_experiment/config.py:48
 
     @property
     def half_bottom_space(self):
@@ -380,3 +382,86 @@ def view_non_collision(poses, scene_points, gripper=None, inverse="general", cou
     if count is not None:
         ok = ok & (torch.arange(K, device=xyz.device).view(1, K) < count.view(B, 1))
     return ok, counts
+
+
+@dataclass
+class FrameEvaluation:
+    """What `eval_frames` returns: (B, K) device tensors, one entry per pose row.  `back`, `finger`, `close`, `n_left`,
+    `n_right` int32; `collision`, `multi_objects` bool; `left_y`, `right_y`, `mean_left`, `mean_right`, `score` fp32.
+    `ints` (B, K, 8) and `floats` (B, K, 5) are the kernel's own output tensors (include/s4g_ops.h has the layout);
+    the named fields are views of them."""
+    ints: torch.Tensor
+    floats: torch.Tensor
+
+    back = property(lambda self: self.ints[..., 0])
+    finger = property(lambda self: self.ints[..., 1])
+    close = property(lambda self: self.ints[..., 2])
+    multi_objects = property(lambda self: self.ints[..., 3] != 0)
+    n_left = property(lambda self: self.ints[..., 4])
+    n_right = property(lambda self: self.ints[..., 5])
+    collision = property(lambda self: self.ints[..., 6] != 0)
+    left_y = property(lambda self: self.floats[..., 0])
+    right_y = property(lambda self: self.floats[..., 1])
+    mean_left = property(lambda self: self.floats[..., 2])
+    mean_right = property(lambda self: self.floats[..., 3])
+    score = property(lambda self: self.floats[..., 4])
+
+
+def eval_frames(poses, scene_points, scene_normals, scene_labels, gripper=None, inverse="general", count=None):
+    """Batched `EvalExpCloud.eval_frame` (eval_experiment/eval_point_cloud.py:39-113): every pose of every scene graded
+    against the scene's dense labelled cloud in one sync-free call -> `FrameEvaluation`.
+
+    poses (B, K, 4, 4) gripper -> global frames; scene_points, scene_normals (B, 3, N) fp32; scene_labels (B, N)
+    int32.  `inverse=` and `count=` as in `view_non_collision` (rows at or past count[b] are not scanned and read
+    zero / False everywhere).  Per pose: the counts behind the palm and in the fingers (equal to `view_non_collision`'s
+    bit for bit), the number of points in the close region, `collision`, `multi_objects` (more than one label in the
+    close region) and, when the region holds at least `gripper.close_region_min_points` points and neither flag is
+    set, the antipodal score mean |n.y| under the left pad times the same under the right pad; else score 0.
+    Normals and labels are inputs, as for the reference, which reads them from a file: normal estimation (open3d),
+    the baseline variant eval_point_cloud_baseline.py and data_gen/ are out of scope."""
+    gripper = gripper or GripperConfig()
+    xyz = _F._f32c(scene_points, "scene_points")
+    nrm = _F._f32c(scene_normals, "scene_normals")
+    if not isinstance(scene_labels, torch.Tensor) or scene_labels.device.type != "cuda":
+        raise RuntimeError("scene_labels must be a CUDA tensor (there is no CPU fallback)")
+    if scene_labels.dtype != torch.int32:
+        raise RuntimeError("scene_labels must be int32, got %s" % scene_labels.dtype)
+    if not isinstance(poses, torch.Tensor) or poses.device.type != "cuda":
+        raise RuntimeError("poses must be a CUDA tensor (there is no CPU fallback)")
+    if xyz.dim() != 3 or xyz.size(1) != 3:
+        raise RuntimeError("scene_points must be (B, 3, N)")
+    B, _, N = xyz.shape
+    if tuple(nrm.shape) != (B, 3, N):
+        raise RuntimeError("scene_normals must be (B, 3, N) like scene_points")
+    if tuple(scene_labels.shape) != (B, N):
+        raise RuntimeError("scene_labels must be (B, N)")
+    if poses.dim() != 4 or poses.size(0) != B or tuple(poses.shape[2:]) != (4, 4):
+        raise RuntimeError("poses must be (B, K, 4, 4)")
+    if len({xyz.device, nrm.device, scene_labels.device, poses.device}) != 1:
+        raise RuntimeError("poses, scene_points, scene_normals and scene_labels must live on one device")
+    if inverse not in ("general", "se3"):
+        raise ValueError("inverse must be 'general' or 'se3'")
+    K = poses.shape[1]
+    dev = xyz.device
+    lab = scene_labels.contiguous()
+    g2l = poses.float().contiguous() if inverse == "se3" else torch.linalg.inv(poses.double()).float().contiguous()
+    cnt = None
+    if count is not None:
+        if tuple(count.shape) != (B,):
+            raise RuntimeError("count must be (B,)")
+        cnt = count.to(device=dev, dtype=torch.int64).contiguous()
+    ints = torch.empty((B, K, 8), dtype=torch.int32, device=dev)
+    floats = torch.empty((B, K, 5), dtype=torch.float32, device=dev)
+    params = (ctypes.c_float * 10)(gripper.finger_length, gripper.bottom_length, gripper.half_hand_thickness,
+                                   gripper.half_bottom_width, gripper.half_bottom_space, gripper.back_collision_margin,
+                                   gripper.back_collision_threshold, gripper.finger_collision_threshold,
+                                   gripper.close_region_min_points, gripper.neighbor_depth)
+    nbytes = _cabi.lib().s4g_eval_frames_workspace_bytes(B, N, K)
+    ws = torch.empty((max(int(nbytes), 1),), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        rc = _cabi.lib().s4g_eval_frames_f32(xyz.data_ptr(), nrm.data_ptr(), lab.data_ptr(), g2l.data_ptr(), B, N, K,
+                                             params, None if cnt is None else cnt.data_ptr(),
+                                             1 if inverse == "se3" else 0, ints.data_ptr(), floats.data_ptr(),
+                                             ws.data_ptr(), int(nbytes), _F._stream())
+    _cabi.check(rc, "eval_frames")
+    return FrameEvaluation(ints, floats)
