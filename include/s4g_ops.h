@@ -60,7 +60,8 @@ extern "C" {
  * 14: S4G_GEMM_LOAD_CHANNEL_FIRST, S4G_GEMM_EPI_MAX_CHANNEL_FIRST and s4g_gemm_desc_t.a_L (any SharedMLP / SA max-pool
  *     on its own (B, C, L) tensors: s4g_release_amd.accelerate), s4g_amax_per_scene_f32.
  *     Added under 14 with no layout change: s4g_eval_frames_f32 / s4g_eval_frames_workspace_bytes (batched antipodal
- *     and collision grading of grasp frames against a labelled scene cloud with normals). */
+ *     and collision grading of grasp frames against a labelled scene cloud with normals); s4g_local_search_f32 /
+ *     s4g_local_search_workspace_bytes (the data generator's per-frame local grasp search). */
 #define S4G_ABI_VERSION 14
 
 /* ---------------------------------------------------------------------------
@@ -717,6 +718,48 @@ int s4g_eval_frames_f32(const float *xyz_b3n, const float *normals_b3n, const in
                         const float *g2l_bk44, int64_t B, int64_t N, int64_t K, const float *params10,
                         const int64_t *pose_count_b, int invert_se3, int32_t *ints_bk8, float *floats_bk5,
                         void *workspace, size_t workspace_bytes, s4g_stream_t stream);
+
+/* Local grasp search of the data generator (csrc/local_search.hip): TorchSingleViewPointCloud.finger_hand with
+ * _table_collision_check and _antipodal_score (data_gen/pcd_classes/torch_single_view_point_cloud.py:152-180,224-358)
+ * for every frame of every scene, without host synchronisation.  Per frame, L approach depths x T rolls about the
+ * frame's x axis = L * T placements, each graded against the scene cloud.
+ * points (B, F, 3) frame origins, frames (B, F, 3, 3) with the x, y, z axes as COLUMNS, xyz / normals (B, 3, N) fp32,
+ * labels (B, N) int32.  frame_count_b (device, may be NULL): only the first frame_count_b[b] rows of scene b are
+ * frames; the others are not scanned and read as invalid.  1 <= L <= 8, 1 <= T <= 16 (S4G_EINVAL otherwise).
+ * params13 (HOST pointer) = {FINGER_LENGTH, BOTTOM_LENGTH, HALF_HAND_THICKNESS, HALF_BOTTOM_WIDTH, HALF_BOTTOM_SPACE,
+ *   BACK_COLLISION_MARGIN, BACK_COLLISION_THRESHOLD, FINGER_COLLISION_THRESHOLD, CLOSE_REGION_MIN_POINTS,
+ *   NEIGHBOR_DEPTH, TABLE_HEIGHT, TABLE_HEIGHT + TABLE_COLLISION_OFFSET, NUM_POINTS_THRESHOLD}
+ *   (data_gen/configs/config.py:17-56,89); no_label = the label of a placement without one (len(NAME_LIST)).
+ * tables_3l2t (DEVICE pointer, 3 L + 2 T floats) = {depth dl[L], slab lower bound dl - BOTTOM_LENGTH [L], slab upper
+ *   bound dl + FINGER_LENGTH [L], cos[T], sin[T]} (config.py:34,44,75-82).
+ * A frame with mean |frame| < 1e-6 or p.z + frame[2][0] * FINGER_LENGTH < TABLE_HEIGHT fails its gate (:257,259): not
+ * scanned, everything reads as for a padding row.  Every inequality is strict, all arithmetic fp32.
+ * Outputs (P = L * T, placement index = depth * T + roll):
+ *   ints_bfp6      int32 (B, F, P, 6) = {search_score, objects_label, back, finger, close, table_collision}: back /
+ *                  finger / close = the points of the depth slab behind the palm / in the fingers / in the close region
+ *                  (:294-321), counted for every placement of a frame that passed its gate and that does not collide with
+ *                  the table (the others are skipped before anything is counted, :288, and read 0); table_collision = a corner
+ *                  of the gripper's box below params[11] (:224-241); search_score = close and objects_label = the
+ *                  region's label where the placement reaches the score -- no table collision, at least params[12]
+ *                  points in the slab, back <= params[6], finger <= params[7], close >= params[8], one label
+ *                  (:273-330) -- else 0 and no_label
+ *   scores_bfp     fp32 (B, F, P): the antipodal score (:167-176) where the placement reaches it, else 0; NaN where a
+ *                  band is empty, as in s4g_eval_frames_f32
+ *   slab_bfl       int32 (B, F, L): points of each depth slab (:270-273)
+ *   valid_bf       int32 (B, F): 1 where the maximum of the frame's scores is not below 1e-4 (:348)
+ *   valid_index_bf int32 (B, F): the valid frames of the scene in ascending order, then -1;  count_b int64 (B): how many
+ * Every frame's row holds its own results only (the reference leaves a rejected frame's entries in the slot the next
+ * frame reuses).  Run-to-run bit-identical and batch invariant: integers and extrema by integer atomics, the band sums
+ * as integers of scale 2^-30 (each |n.y| clamped to 4), no floating-point atomics.  N < 2^30, B and F <= 65 535.
+ * Workspace: s4g_local_search_workspace_bytes(B, N, F, L, T) bytes, 256-byte aligned; contents need not be
+ * initialised. */
+size_t s4g_local_search_workspace_bytes(int64_t B, int64_t N, int64_t F, int64_t L, int64_t T);
+int s4g_local_search_f32(const float *points_bf3, const float *frames_bf33, const float *xyz_b3n,
+                         const float *normals_b3n, const int32_t *labels_bn, int64_t B, int64_t N, int64_t F,
+                         int64_t L, int64_t T, const float *params13, int32_t no_label, const float *tables_3l2t,
+                         const int64_t *frame_count_b, int32_t *ints_bfp6, float *scores_bfp, int32_t *slab_bfl,
+                         int32_t *valid_bf, int32_t *valid_index_bf, int64_t *count_b, void *workspace,
+                         size_t workspace_bytes, s4g_stream_t stream);
 
 /* ---- next row f3: cloud pre-processing on device -------------------------
  * Single-scene passes in front of the network (reference

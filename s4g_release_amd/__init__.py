@@ -14,3 +14,10 @@ def accelerate(net, precision="f16x2"):
     the HIP contraction kernels; returns the qualified names of the converted modules.  See `accelerated.py`."""
     from .accelerated import accelerate as _accelerate
     return _accelerate(net, precision)
+
+
+def grade_local_search(*args, **kwargs):
+    """The data generator's per-frame local grasp search for every frame of every scene in one call: the S4G labels.
+    See `postprocess.grade_local_search`."""
+    from .postprocess import grade_local_search as _grade
+    return _grade(*args, **kwargs)

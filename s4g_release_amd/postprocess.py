@@ -465,3 +465,212 @@ def eval_frames(poses, scene_points, scene_normals, scene_labels, gripper=None, 
                                              ws.data_ptr(), int(nbytes), _F._stream())
     _cabi.check(rc, "eval_frames")
     return FrameEvaluation(ints, floats)
+
+
+LS_MAX_DEPTHS, LS_MAX_ANGLES = 8, 16        # the compiled maxima of csrc/local_search.hip
+
+
+@dataclass
+class LocalSearchConfig:
+    """The constants of the data generator's local search (data_gen/configs/config.py:17-56,89) and the label of a
+    placement without one (`len(NAME_LIST)`, torch_single_view_point_cloud.py:74-75)."""
+    table_height: float = 0.75
+    num_points_threshold: float = 8
+    length_search: tuple = (-0.08, -0.06, -0.04, -0.02)
+    thickness_search: tuple = (0,)
+    theta_search_deg: tuple = tuple(range(-90, 90, 15))
+    back_collision_threshold: float = 0 * math.sqrt(8)
+    back_collision_margin: float = 0.0
+    finger_collision_threshold: float = 0
+    close_region_min_points: float = 10
+    neighbor_depth: float = 0.005
+    half_bottom_width: float = 0.057
+    bottom_length: float = 0.08
+    finger_width: float = 0.023
+    half_hand_thickness: float = 0.012
+    finger_length: float = 0.09
+    table_collision_offset: float = 0.005
+    no_label: int = 122
+
+    @property
+    def half_bottom_space(self):
+        return self.half_bottom_width - self.finger_width
+
+    @property
+    def shape(self):
+        """(L, T): depths and roll angles per depth (GRASP_PER_LENGTH)."""
+        return len(self.length_search), len(self.theta_search_deg) * len(self.thickness_search)
+
+    def check(self):
+        if len(self.thickness_search) != 1 or float(self.thickness_search[0]) != 0.0:
+            raise ValueError("THICKNESS_SEARCH must stay [0], the only value the reference ships: a non-zero height "
+                             "is not implemented")
+        L, T = self.shape
+        if not (1 <= L <= LS_MAX_DEPTHS and 1 <= T <= LS_MAX_ANGLES):
+            raise ValueError("need 1..%d depths and 1..%d angles, got %d and %d" % (LS_MAX_DEPTHS, LS_MAX_ANGLES, L, T))
+
+    def tables(self):
+        """The fp32 values the reference works with, formed as it forms them: theta = deg / 57.29578 in Python floats
+        (config.py:44), rows (length, theta, height) to one fp32 tensor (:74), torch.cos / torch.sin of its theta
+        column (:79-82).  -> dict of fp32 CPU tensors `depth` (L), `cos`, `sin` (T), and the slab bounds `lo`, `hi` (L)
+        = dl - BOTTOM_LENGTH, dl + FINGER_LENGTH in Python floats, rounded once (:270-271)."""
+        self.check()
+        rows = [(float(length), deg / 57.29578, float(h)) for length in self.length_search
+                for deg in self.theta_search_deg for h in self.thickness_search]
+        a = torch.tensor(rows)
+        L, T = self.shape
+        cos, sin = torch.cos(a[:, 1])[:T].clone(), torch.sin(a[:, 1])[:T].clone()
+        return {"depth": a[::T, 0].clone(), "cos": cos, "sin": sin,
+                "lo": torch.tensor([float(v) - self.bottom_length for v in self.length_search]),
+                "hi": torch.tensor([float(v) + self.finger_length for v in self.length_search])}
+
+    def search_to_local(self):
+        """LOCAL_SEARCH_TO_LOCAL (config.py:88) as (L, T, 4, 4) fp32, formed directly instead of by `torch.inverse`: the
+        inverse roll and the shift dl along x."""
+        tb = self.tables()
+        L, T = self.shape
+        S = torch.zeros(L, T, 4, 4)
+        S[..., 0, 0] = S[..., 3, 3] = 1.0
+        S[..., 0, 3] = tb["depth"].view(L, 1)
+        S[..., 1, 1] = S[..., 2, 2] = tb["cos"].view(1, T)
+        S[..., 1, 2] = -tb["sin"].view(1, T)
+        S[..., 2, 1] = tb["sin"].view(1, T)
+        return S
+
+
+@dataclass
+class LocalSearch:
+    """What `grade_local_search` returns: device tensors, one row per frame.  `ints` (B, F, L, T, 6), `scores`
+    (B, F, L, T), `slab_count` (B, F, L), `valid_index` (B, F) and `count` (B,) are the kernel's own outputs
+    (include/s4g_ops.h has the layout); the named fields are views of them."""
+    ints: torch.Tensor
+    scores: torch.Tensor
+    slab_count: torch.Tensor
+    valid_i32: torch.Tensor
+    valid_index: torch.Tensor
+    count: torch.Tensor
+    points: torch.Tensor
+    frames: torch.Tensor
+    config: LocalSearchConfig
+    unbatched: bool = False
+
+    search_score = property(lambda self: self.ints[..., 0])
+    objects_label = property(lambda self: self.ints[..., 1])
+    back = property(lambda self: self.ints[..., 2])
+    finger = property(lambda self: self.ints[..., 3])
+    close = property(lambda self: self.ints[..., 4])
+    table_collision = property(lambda self: self.ints[..., 5] != 0)
+    antipodal_score = property(lambda self: self.scores)
+    valid = property(lambda self: self.valid_i32 != 0)
+
+    def frames_of(self, index=None):
+        """The reference's `valid_frame` (:351-356) of the frames `index` (B, M) (default: `valid_index`): (B, M, L, T,
+        4, 4) = [R | p] @ LOCAL_SEARCH_TO_LOCAL, formed directly (no `torch.inverse`).  Rows whose index is -1 are 0."""
+        index = self.valid_index if index is None else index
+        idx = index.to(device=self.points.device, dtype=torch.int64)
+        B, F = self.points.shape[:2]
+        M = idx.shape[1]
+        live = (idx >= 0).view(B, M, 1, 1, 1, 1)
+        g = idx.clamp(min=0)
+        H = torch.zeros((B, M, 4, 4), dtype=torch.float32, device=self.points.device)
+        H[..., :3, :3] = torch.gather(self.frames, 1, g.view(B, M, 1, 1).expand(B, M, 3, 3))
+        H[..., :3, 3] = torch.gather(self.points, 1, g.view(B, M, 1).expand(B, M, 3))
+        H[..., 3, 3] = 1.0
+        S = _small_on_device(self.config.search_to_local(), torch.float32, self.points.device)
+        return torch.where(live, torch.matmul(H.view(B, M, 1, 1, 4, 4), S), torch.zeros((), device=H.device))
+
+    def dump(self, b=0):
+        """The dictionary of the reference's `dump()` (:203-222) for scene b, in the world frame (the camera transform is
+        the caller's); `point_cloud` holds the frame origins (3, F).  Reads the count on the host."""
+        n = int(self.count[b])
+        vi = self.valid_index[b, :n].long()
+        return {"search_score": self.search_score[b, vi].cpu().numpy(),
+                "antipodal_score": self.antipodal_score[b, vi].cpu().numpy(),
+                "objects_label": self.objects_label[b, vi].to(torch.int16).cpu().numpy(),
+                "point_cloud": self.points[b].t().contiguous().cpu().numpy(),
+                "valid_index": vi.int().cpu().numpy(),
+                "valid_frame": self.frames_of(self.valid_index[b:b + 1, :n])[0].cpu().numpy()
+                if n else torch.zeros((0,) + self.config.shape + (4, 4)).numpy()}
+
+
+def grade_local_search(points, frames, scene_points, scene_normals, scene_labels, config=None, frame_count=None):
+    """The data generator's per-point local grasp search -- `TorchSingleViewPointCloud.finger_hand` with
+    `_table_collision_check` and `_antipodal_score` (data_gen/pcd_classes/torch_single_view_point_cloud.py:152-180,
+    224-358), which `run_score` (:198-201) loops over the frames -- for every frame of every scene in one sync-free,
+    graph-capturable call -> `LocalSearch`.
+
+    points (B, F, 3) frame origins and frames (B, F, 3, 3) with the x, y, z axes as columns (`self.frame`; frame
+    estimation is out of scope, as for `TorchPrecomputedSingleViewPointCloud`); scene_points, scene_normals (B, 3, N)
+    fp32; scene_labels (B, N) int32; unbatched inputs get a leading 1.  frame_count (B,) on the device (optional): only
+    the first frame_count[b] rows of scene b are frames, the others are not scanned and read as invalid.  Per frame,
+    L x T placements (4 depths x 12 rolls as shipped): `search_score`, `objects_label`, `antipodal_score`,
+    `table_collision`, the counts `back` / `finger` / `close` behind every verdict (0 where the table gate skips), `slab_count` per depth, `valid`,
+    and per scene the ascending `valid_index` (padded with -1) and `count`.
+
+    Three decisions differ from running the reference as written.  (1) No stale slots: the reference writes a frame's
+    results into slot `valid_grasp` and does not clear it when the frame is rejected, so they leak into the next
+    accepted frame wherever that one skips a placement; here every frame's row holds its own results only.  (2) A
+    close region whose points all share one y gives empty bands: the score is NaN, as `eval_frames` gives (the frame
+    then counts as valid, as `torch.max` of a NaN does in the reference).  (3) `valid_frame` is formed directly
+    (`LocalSearch.frames_of`), without `torch.inverse`; THICKNESS_SEARCH stays [0]."""
+    cfg = config or LocalSearchConfig()
+    cfg.check()
+    for name, t in (("points", points), ("frames", frames), ("scene_labels", scene_labels)):
+        if not isinstance(t, torch.Tensor) or t.device.type != "cuda":
+            raise RuntimeError("%s must be a CUDA tensor (there is no CPU fallback)" % name)
+    unbatched = points.dim() == 2
+    if unbatched:
+        points, frames = points[None], frames[None]
+        scene_points, scene_normals, scene_labels = scene_points[None], scene_normals[None], scene_labels[None]
+    xyz = _F._f32c(scene_points, "scene_points")
+    nrm = _F._f32c(scene_normals, "scene_normals")
+    if scene_labels.dtype != torch.int32:
+        raise RuntimeError("scene_labels must be int32, got %s" % scene_labels.dtype)
+    if points.dtype != torch.float32 or frames.dtype != torch.float32:
+        raise RuntimeError("points and frames must be float32")
+    if xyz.dim() != 3 or xyz.size(1) != 3:
+        raise RuntimeError("scene_points must be (B, 3, N)")
+    B, _, N = xyz.shape
+    if tuple(nrm.shape) != (B, 3, N):
+        raise RuntimeError("scene_normals must be (B, 3, N) like scene_points")
+    if tuple(scene_labels.shape) != (B, N):
+        raise RuntimeError("scene_labels must be (B, N)")
+    if points.dim() != 3 or points.size(0) != B or points.size(2) != 3:
+        raise RuntimeError("points must be (B, F, 3)")
+    F = points.shape[1]
+    if tuple(frames.shape) != (B, F, 3, 3):
+        raise RuntimeError("frames must be (B, F, 3, 3)")
+    if len({xyz.device, nrm.device, scene_labels.device, points.device, frames.device}) != 1:
+        raise RuntimeError("points, frames, scene_points, scene_normals and scene_labels must live on one device")
+    dev = xyz.device
+    pts, frm, lab = points.contiguous(), frames.contiguous(), scene_labels.contiguous()
+    cnt = None
+    if frame_count is not None:
+        if tuple(frame_count.shape) != (B,):
+            raise RuntimeError("frame_count must be (B,)")
+        cnt = frame_count.to(device=dev, dtype=torch.int64).contiguous()
+    L, T = cfg.shape
+    tb = cfg.tables()
+    tables = _small_on_device(torch.cat([tb["depth"], tb["lo"], tb["hi"], tb["cos"], tb["sin"]]), torch.float32, dev)
+    ints = torch.empty((B, F, L, T, 6), dtype=torch.int32, device=dev)
+    scores = torch.empty((B, F, L, T), dtype=torch.float32, device=dev)
+    slab = torch.empty((B, F, L), dtype=torch.int32, device=dev)
+    valid = torch.empty((B, F), dtype=torch.int32, device=dev)
+    valid_index = torch.empty((B, F), dtype=torch.int32, device=dev)
+    count = torch.empty((B,), dtype=torch.int64, device=dev)
+    params = (ctypes.c_float * 13)(cfg.finger_length, cfg.bottom_length, cfg.half_hand_thickness, cfg.half_bottom_width,
+                                   cfg.half_bottom_space, cfg.back_collision_margin, cfg.back_collision_threshold,
+                                   cfg.finger_collision_threshold, cfg.close_region_min_points, cfg.neighbor_depth,
+                                   cfg.table_height, cfg.table_height + cfg.table_collision_offset,
+                                   cfg.num_points_threshold)
+    nbytes = _cabi.lib().s4g_local_search_workspace_bytes(B, N, F, L, T)
+    ws = torch.empty((max(int(nbytes), 1),), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        rc = _cabi.lib().s4g_local_search_f32(pts.data_ptr(), frm.data_ptr(), xyz.data_ptr(), nrm.data_ptr(),
+                                              lab.data_ptr(), B, N, F, L, T, params, int(cfg.no_label),
+                                              tables.data_ptr(), None if cnt is None else cnt.data_ptr(),
+                                              ints.data_ptr(), scores.data_ptr(), slab.data_ptr(), valid.data_ptr(),
+                                              valid_index.data_ptr(), count.data_ptr(), ws.data_ptr(), int(nbytes),
+                                              _F._stream())
+    _cabi.check(rc, "local_search")
+    return LocalSearch(ints, scores, slab, valid, valid_index, count, pts, frm, cfg, unbatched)
