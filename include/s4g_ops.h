@@ -61,7 +61,8 @@ extern "C" {
  *     on its own (B, C, L) tensors: s4g_release_amd.accelerate), s4g_amax_per_scene_f32.
  *     Added under 14 with no layout change: s4g_eval_frames_f32 / s4g_eval_frames_workspace_bytes (batched antipodal
  *     and collision grading of grasp frames against a labelled scene cloud with normals); s4g_local_search_f32 /
- *     s4g_local_search_workspace_bytes (the data generator's per-frame local grasp search). */
+ *     s4g_local_search_workspace_bytes (the data generator's per-frame local grasp search); s4g_darboux_frames_f32 /
+ *     s4g_darboux_frames_workspace_bytes (the Darboux frames that search starts from). */
 #define S4G_ABI_VERSION 14
 
 /* ---------------------------------------------------------------------------
@@ -760,6 +761,45 @@ int s4g_local_search_f32(const float *points_bf3, const float *frames_bf33, cons
                          const int64_t *frame_count_b, int32_t *ints_bfp6, float *scores_bfp, int32_t *slab_bfl,
                          int32_t *valid_bf, int32_t *valid_index_bf, int64_t *count_b, void *workspace,
                          size_t workspace_bytes, s4g_stream_t stream);
+
+/* Darboux frames of the data generator's label search (csrc/darboux.hip): TorchSingleViewPointCloud._estimate_frame
+ * (data_gen/pcd_classes/torch_single_view_point_cloud.py:107-133) for every frame row of every scene, without host
+ * synchronisation.  xyz / normals (B, 3, N) fp32, the normals used as given (not re-normalised); frame_index (B, F)
+ * int32 indices into the cloud.  A row is PADDING where its index is negative or >= N, or where frame_count_b (device,
+ * may be NULL) is given and f >= frame_count_b[b]: frame and point 0, count 0, flags 0.
+ * Per frame row, i = frame_index[b][f], n = normals[:, i]:
+ *   neighbours = every point j of scene b with squared distance < radius * radius (fp32 product; the subtraction,
+ *     squares and sum in fp32, each op rounded on its own; strict), i itself included; any number of them;
+ *   c = (I - n n^T) mean_j(n_j), cov = sum_j (n_j - c)(n_j - c)^T (:122-125: the mean is projected, the n_j are not),
+ *     both accumulated in double in an order fixed by the scene, cov rounded to fp32 once (scaled by its trace);
+ *   v0 = the eigenvector of cov's smallest eigenvalue (cyclic Jacobi in fp32), minor = normalise(v0 - (v0 . n) n),
+ *     principal = minor x n, the frame's COLUMNS = [-n, -principal, minor] (:126-133), formed in double, rounded once.
+ * Eigenvector sign (the reference leaves it to LAPACK): of the unnormalised minor axis v0 - (v0 . n) n the component
+ *   with the largest magnitude is positive, the lowest index winning a tie.  The other sign flips columns y and z
+ *   together: a half turn about the approach axis.
+ * count < min_neighbours: the identity frame, as the reference leaves it (:118-120), flags 0.
+ * Degenerate rows: the unnormalised minor axis has squared norm below 1e-12 (v0 parallel to n), or the point, its
+ *   normal or a neighbour's normal is not finite (the reference gives NaN): the ZERO frame, which
+ *   s4g_local_search_f32's gate rejects, and flags bit 1.  The point is written as given.
+ * Outputs: frames_bf33 fp32 (B, F, 3, 3) row-major, axes as columns; points_bf3 fp32 (B, F, 3) = xyz[:, i];
+ *   count_bf int32 (B, F) = the neighbour count k; flags_bf int32 (B, F): bit 0 = a frame was estimated, bit 1 =
+ *   degenerate.
+ * Run-to-run bit-identical and batch invariant: no atomics touch a sum, every cell of the neighbour grid is read in
+ * ascending point index.  A scene outside the grid's exactness range (a coordinate further than about 4 000 radii
+ * from the scene's first point, or not finite) or with N > 65 536 is scanned in index order: the same neighbour sets;
+ * the sums run in another order, so the last bits may differ from the grid's.
+ * Cost: a frame reads the points of its 27 cells twice, and the ordering pass ranks every point against the points
+ * of its own cell, so both grow with the square of a cell's population: linear in N for a view sampled at about the
+ * radius (tens of points per cell), and of the order of N * N point reads where a whole scene falls into one cell
+ * (4e9 for 65 536 points inside one radius -- the same order as the F * k reads the frames themselves then need).
+ * radius in (0, 1e18), min_neighbours >= 1, N and F < 2^30, B <= 65 535 (S4G_EINVAL otherwise).
+ * Workspace: s4g_darboux_frames_workspace_bytes(B, N, F) bytes (0 for N > 65 536), 256-byte aligned; contents need
+ * not be initialised. */
+size_t s4g_darboux_frames_workspace_bytes(int64_t B, int64_t N, int64_t F);
+int s4g_darboux_frames_f32(const float *xyz_b3n, const float *normals_b3n, const int32_t *frame_index_bf,
+                           const int64_t *frame_count_b, int64_t B, int64_t N, int64_t F, float radius,
+                           int32_t min_neighbours, float *frames_bf33, float *points_bf3, int32_t *count_bf,
+                           int32_t *flags_bf, void *workspace, size_t workspace_bytes, s4g_stream_t stream);
 
 /* ---- next row f3: cloud pre-processing on device -------------------------
  * Single-scene passes in front of the network (reference

@@ -21,3 +21,17 @@ def grade_local_search(*args, **kwargs):
     See `postprocess.grade_local_search`."""
     from .postprocess import grade_local_search as _grade
     return _grade(*args, **kwargs)
+
+
+def estimate_frames(*args, **kwargs):
+    """The data generator's Darboux frames for every frame of every scene in one call.  See
+    `postprocess.estimate_frames`."""
+    from .postprocess import estimate_frames as _estimate
+    return _estimate(*args, **kwargs)
+
+
+def label_view(*args, **kwargs):
+    """View cloud with normals in, S4G labels out: the sampled indices, `estimate_frames` and `grade_local_search` in
+    one call.  See `postprocess.label_view`."""
+    from .postprocess import label_view as _label
+    return _label(*args, **kwargs)

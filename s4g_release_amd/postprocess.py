@@ -674,3 +674,150 @@ def grade_local_search(points, frames, scene_points, scene_normals, scene_labels
                                               _F._stream())
     _cabi.check(rc, "local_search")
     return LocalSearch(ints, scores, slab, valid, valid_index, count, pts, frm, cfg, unbatched)
+
+
+CURVATURE_RADIUS = 0.01                    # data_gen/configs/config.py:37
+SAMPLE_REGION_OFFSET = 0.015               # SAMPLE_REGION = TABLE_HEIGHT + 0.015 (config.py:18)
+
+
+@dataclass
+class DarbouxFrames:
+    """What `estimate_frames` returns: device tensors, one row per frame.  `frames` (B, F, 3, 3) with the axes as
+    columns, `points` (B, F, 3), `count` (B, F) the neighbour count, `flags` (B, F) the kernel's own (bit 0 =
+    estimated, bit 1 = degenerate), `frame_index` (B, F) int32 padded with -1 and `frame_count` (B,) int64 or None."""
+    frames: torch.Tensor
+    points: torch.Tensor
+    count: torch.Tensor
+    flags: torch.Tensor
+    frame_index: torch.Tensor
+    frame_count: torch.Tensor
+    unbatched: bool = False
+
+    estimated = property(lambda self: (self.flags & 1) != 0)
+    degenerate = property(lambda self: (self.flags & 2) != 0)
+
+
+def sample_frame_index(cloud, sample_region):
+    """`frame_indices` of the reference (torch_single_view_point_cloud.py:53) per scene, without a sync: cloud (B, 3, N)
+    -> (B, N) int32 ascending indices of the points with z > sample_region, then -1, and their number (B,) int64."""
+    B, _, N = cloud.shape
+    above = cloud[:, 2, :] > sample_region
+    count = above.sum(1)
+    # a stable sort of "not above" keeps the chosen points in front, each group in ascending index
+    order = torch.sort((~above).to(torch.uint8), dim=1, stable=True).indices
+    live = torch.arange(N, device=cloud.device).view(1, N) < count.view(B, 1)
+    return torch.where(live, order, order.new_full((), -1)).to(torch.int32), count
+
+
+def estimate_frames(cloud, normals, frame_index=None, frame_count=None, radius=CURVATURE_RADIUS, min_neighbours=5,
+                    sample_region=None):
+    """The data generator's Darboux frames -- `TorchSingleViewPointCloud._estimate_frame`
+    (data_gen/pcd_classes/torch_single_view_point_cloud.py:107-133), which `estimate_frames` (:98-105) loops over the
+    sampled points with a kd-tree radius query and an `eigh` each -- for every frame of every scene in one sync-free,
+    graph-capturable call -> `DarbouxFrames`, whose `points`, `frames` and `frame_count` are `grade_local_search`'s
+    inputs.
+
+    cloud, normals (B, 3, N) fp32, the normals used as given.  One scene may be passed unbatched -- cloud, normals
+    (3, N) and frame_index (F,) -- and gets a leading 1: the result is ALWAYS batched (B = 1 then, `unbatched` set,
+    as `grade_local_search` does) and frame_count is always (B,).  frame_index (B, F)
+    int32 indices into the cloud, a negative one marking a padding row; frame_count (B,) on the device (optional): the
+    rows at or past it are padding.  frame_index=None takes the reference's `frame_indices` (:53): the ascending
+    indices of the points with z > sample_region (default TABLE_HEIGHT + 0.015 of `LocalSearchConfig`), F = N rows
+    padded with -1, and their count.  Per frame: the neighbours with squared distance < radius^2 (the point itself
+    included, any number), the covariance of their normals about the projected mean (:122-125), the eigenvector of
+    its smallest eigenvalue, columns [-n, -principal, minor] (:126-133).
+
+    Three decisions.  (1) Fewer than min_neighbours neighbours: the identity frame, as the reference leaves it
+    (:118-120); `count` tells.  (2) A frame whose eigenvector is parallel to the normal, or whose inputs are not finite
+    (NaN in the reference): the zero frame, which `grade_local_search` rejects, and `degenerate`.  (3) The
+    eigenvector's sign, which the reference leaves to LAPACK: the largest component of the unnormalised minor axis is
+    positive, the lowest index winning a tie.  The other sign turns the frame half a turn about its approach axis,
+    which maps the placement at roll theta onto the one at -theta."""
+    for name, t in (("cloud", cloud), ("normals", normals)):
+        if not isinstance(t, torch.Tensor) or t.device.type != "cuda":
+            raise RuntimeError("%s must be a CUDA tensor (there is no CPU fallback)" % name)
+    if not float(radius) > 0.0:
+        raise ValueError("radius must be positive, got %r" % (radius,))
+    if int(min_neighbours) < 1:
+        raise ValueError("min_neighbours must be at least 1, got %r" % (min_neighbours,))
+    if frame_index is not None and (not isinstance(frame_index, torch.Tensor) or frame_index.device.type != "cuda"):
+        raise RuntimeError("frame_index must be a CUDA tensor (there is no CPU fallback)")
+    unbatched = cloud.dim() == 2
+    if unbatched:                       # one scene: (3, N), (3, N), (F,); frame_count stays (1,), as for grade_local_search
+        cloud, normals = cloud[None], normals[None]
+        frame_index = None if frame_index is None else frame_index[None]
+    xyz = _F._f32c(cloud, "cloud")
+    nrm = _F._f32c(normals, "normals")
+    if xyz.dim() != 3 or xyz.size(1) != 3 or xyz.size(2) < 1:
+        raise RuntimeError("cloud must be (B, 3, N)")
+    B, _, N = xyz.shape
+    if tuple(nrm.shape) != (B, 3, N):
+        raise RuntimeError("normals must be (B, 3, N) like cloud")
+    dev = xyz.device
+    if frame_index is None:
+        if frame_count is not None:
+            raise RuntimeError("frame_count needs a frame_index")
+        if sample_region is None:
+            sample_region = LocalSearchConfig().table_height + SAMPLE_REGION_OFFSET
+        index, cnt = sample_frame_index(xyz, float(sample_region))
+    else:
+        if frame_index.dtype != torch.int32:
+            raise RuntimeError("frame_index must be int32, got %s" % frame_index.dtype)
+        if frame_index.dim() != 2 or frame_index.size(0) != B:
+            raise RuntimeError("frame_index must be (B, F)")
+        index, cnt = frame_index.contiguous(), None
+        if frame_count is not None:
+            if tuple(frame_count.shape) != (B,):
+                raise RuntimeError("frame_count must be (B,)")
+            cnt = frame_count.to(device=dev, dtype=torch.int64).contiguous()
+    if len({xyz.device, nrm.device, index.device}) != 1:
+        raise RuntimeError("cloud, normals and frame_index must live on one device")
+    F = index.shape[1]
+    frames = torch.empty((B, F, 3, 3), dtype=torch.float32, device=dev)
+    points = torch.empty((B, F, 3), dtype=torch.float32, device=dev)
+    count = torch.empty((B, F), dtype=torch.int32, device=dev)
+    flags = torch.empty((B, F), dtype=torch.int32, device=dev)
+    nbytes = _cabi.lib().s4g_darboux_frames_workspace_bytes(B, N, F)
+    ws = torch.empty((max(int(nbytes), 1),), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        rc = _cabi.lib().s4g_darboux_frames_f32(xyz.data_ptr(), nrm.data_ptr(), index.data_ptr(),
+                                                None if cnt is None else cnt.data_ptr(), B, N, F, float(radius),
+                                                int(min_neighbours), frames.data_ptr(), points.data_ptr(),
+                                                count.data_ptr(), flags.data_ptr(), ws.data_ptr(), int(nbytes),
+                                                _F._stream())
+    _cabi.check(rc, "darboux_frames")
+    return DarbouxFrames(frames, points, count, flags, index, cnt, unbatched)
+
+
+def map_cloud_index(valid_index, frame_index):
+    """`valid_index` as the reference stores it (:357): the CLOUD index of each valid frame.  valid_index (B, F) frame
+    rows padded with -1 (what `grade_local_search` reports), frame_index (B, F) -> (B, F) int32, -1 where padded."""
+    live = valid_index >= 0
+    got = torch.gather(frame_index, 1, valid_index.clamp(min=0).to(torch.int64))
+    return torch.where(live, got, got.new_full((), -1))
+
+
+@dataclass
+class ViewLabels:
+    """What `label_view` returns: the `LocalSearch` of the view's frames, the `DarbouxFrames` they came from and
+    `cloud_index` (B, F): the cloud indices of the valid frames in ascending order, then -1 (`search.count` of them)."""
+    search: LocalSearch
+    darboux: DarbouxFrames
+    cloud_index: torch.Tensor
+
+
+def label_view(cloud, normals, scene_points, scene_normals, scene_labels, config=None, frame_index=None,
+               frame_count=None, radius=CURVATURE_RADIUS, min_neighbours=5):
+    """`TorchSingleViewPointCloud.run_score(scene, match_normal=False)` (:182-201): view cloud with normals in, S4G
+    labels out, in one sync-free call -- the sampled indices (:53, z > config.table_height + 0.015, unless frame_index
+    is given), `estimate_frames`, then `grade_local_search` on its points and frames with its frame count ->
+    `ViewLabels`.  cloud, normals (B, 3, N) are the view; scene_points, scene_normals (B, 3, M) and scene_labels
+    (B, M) the dense scene the placements are graded against (the view itself in the reference's eval mode).  One
+    unbatched view (3, N) gets a leading 1, with its scene if that is unbatched too; the results are always batched."""
+    cfg = config or LocalSearchConfig()
+    d = estimate_frames(cloud, normals, frame_index, frame_count, radius, min_neighbours,
+                        sample_region=cfg.table_height + SAMPLE_REGION_OFFSET)
+    if d.unbatched and scene_points.dim() == 2:          # one view against one unbatched scene; a (1, ...) scene passes as is
+        scene_points, scene_normals, scene_labels = scene_points[None], scene_normals[None], scene_labels[None]
+    s = grade_local_search(d.points, d.frames, scene_points, scene_normals, scene_labels, cfg, d.frame_count)
+    return ViewLabels(s, d, map_cloud_index(s.valid_index, d.frame_index))
