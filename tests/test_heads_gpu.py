@@ -7,79 +7,34 @@ import pytest
 import torch
 
 from tests import golden_util as GU
+from tests import heads_ref as H
 
 pytestmark = pytest.mark.gpu
-CH = (3, 9, 4, 5)
+CH = H.CH
 
 
-def _layers(dev, seed):
-    from s4g_release_amd.fused import _Layer
-    g = torch.Generator(device="cpu").manual_seed(seed)
-    r = lambda *s: torch.randn(*s, generator=g)
-    W0 = (r(2048, 256) / 16).to(dev)
-    W1 = (r(4, 256, 512) / 512 ** 0.5).to(dev)
-    W2 = (r(4, 256, 256) / 16).to(dev)
-    W3 = (r(4, 128, 256) / 16).to(dev)
-    WL = torch.zeros(4, 32, 128)
-    bL = torch.zeros(4, 32)
-    for h, c in enumerate(CH):
-        WL[h, :c] = r(c, 128) / 128 ** 0.5
-        bL[h, :c] = r(c)
-    b = [r(2048).to(dev), r(4, 256).to(dev), r(4, 256).to(dev), r(4, 128).to(dev), bL.to(dev)]
-    Ws = [W0, W1, W2, W3, WL.to(dev)]
-    layers = [_Layer(W0, b[0], 256)] + [_Layer(Ws[i], b[i], Ws[i].shape[-1], groups=4) for i in range(1, 5)]
-    return Ws, b, layers
+@pytest.fixture(scope="module")
+def layer_set(dev):
+    """The packed layer sets of this module, built once per seed (`_Layer` / `fragment_order` are the expensive part)."""
+    cache = {}
 
-
-def _run(dev, layers, X, B, N, precision, amax=None, floor=0.0):
-    from s4g_release_amd import _cabi
-    d = _cabi.HeadsDesc()
-    d.precision = precision
-    d.P, d.N, d.ldx = B * N, N, X.shape[1]
-    d.C, d.H0, d.H1, d.H2, d.H3 = 256, 512, 256, 256, 128
-    d.X = X.data_ptr()
-    for l, layer in enumerate(layers):
-        d.W_frag[l] = (layer.Wfrag_bf16 if precision == 2 else layer.Wfrag).data_ptr()
-        d.bias[l] = layer.bias.data_ptr()
-        d.w_inv_scale[l] = layer.w_inv_scale.data_ptr()
-    outs = [torch.full((B, c, N), float("nan"), device=dev) for c in CH]
-    for h, o in enumerate(outs):
-        d.out[h] = o.data_ptr()
-        d.channels[h] = CH[h]
-    d.sigmoid_head = 3
-    d.a_amax = None if amax is None else amax.data_ptr()
-    d.a_amax_floor = floor
-    d.rows_per_scene = N
-    rc = _cabi.lib().s4g_heads_chain_f32(ctypes.byref(d), torch.cuda.current_stream().cuda_stream)
-    _cabi.check(rc, "heads")
-    torch.cuda.synchronize()
-    return outs
-
-
-def _reference(Ws, b, X, B, N, rnd=lambda t: t.double()):
-    outs = []
-    x = rnd(X)
-    for h, c in enumerate(CH):
-        y = (x @ rnd(Ws[0][h * 512:(h + 1) * 512]).t() + b[0][h * 512:(h + 1) * 512].double()).clamp_min(0)
-        for l in (1, 2, 3):
-            y = (rnd(y.float()) @ rnd(Ws[l][h]).t() + b[l][h].double()).clamp_min(0)
-        o = rnd(y.float()) @ rnd(Ws[4][h, :c]).t() + b[4][h, :c].double()
-        if h == 3:
-            o = torch.sigmoid(o)
-        outs.append(o.view(B, N, c).permute(0, 2, 1))
-    return outs
+    def get(seed):
+        if seed not in cache:
+            cache[seed] = H.build_layers(dev, seed)
+        return cache[seed]
+    return get
 
 
 @pytest.mark.parametrize("B,N", [(2, 100), (1, 64), (3, 171)])
-def test_heads_chain_f16x2_is_fp32_class(dev, B, N):
-    Ws, b, layers = _layers(dev, 7 + N)
+def test_heads_chain_f16x2_is_fp32_class(dev, layer_set, B, N):
+    Ws, b, layers = layer_set(7 + N)
     g = torch.Generator(device="cpu").manual_seed(N)
     X = (torch.randn(B * N, 256, generator=g) * torch.tensor([1.0, 40.0, 0.02])[:B, None]
          .repeat_interleave(N, dim=0)).to(dev)      # scenes of very different magnitude
     amax = torch.zeros((B, 64), device=dev)
     amax[:, 5] = X.view(B, -1).abs().amax(dim=1)
-    outs = _run(dev, layers, X, B, N, 3, amax=amax)
-    ref = _reference(Ws, b, X, B, N)
+    outs = H.run(dev, layers, X, B, N, 3, amax=amax)
+    ref = H.reference(Ws, b, X, B, N)
     for h in range(4):
         assert torch.isfinite(outs[h]).all()
         err = (outs[h].double() - ref[h]).abs()
@@ -87,13 +42,13 @@ def test_heads_chain_f16x2_is_fp32_class(dev, B, N):
         assert (err / scale).max().item() < 2e-5, (h, (err / scale).max().item())
 
 
-def test_heads_chain_bf16_matches_a_reference_rounded_at_the_same_points(dev):
+def test_heads_chain_bf16_matches_a_reference_rounded_at_the_same_points(dev, layer_set):
     B, N = 2, 150
-    Ws, b, layers = _layers(dev, 3)
+    Ws, b, layers = layer_set(3)
     X = torch.randn(B * N, 256, generator=torch.Generator(device="cpu").manual_seed(1)).to(dev)
-    outs = _run(dev, layers, X, B, N, 2)
-    ref = _reference(Ws, b, X, B, N, rnd=lambda t: t.to(torch.bfloat16).double())
-    exact = _reference(Ws, b, X, B, N)
+    outs = H.run(dev, layers, X, B, N, 2)
+    ref = H.reference(Ws, b, X, B, N, rnd=lambda t: t.to(torch.bfloat16).double())
+    exact = H.reference(Ws, b, X, B, N)
     for h in range(4):
         scale = max(1.0, ref[h].abs().max().item())
         assert torch.isfinite(outs[h]).all()
@@ -104,7 +59,6 @@ def test_heads_chain_bf16_matches_a_reference_rounded_at_the_same_points(dev):
 
 def test_heads_chain_rejects_other_widths_and_bad_arguments(dev):
     from s4g_release_amd import _cabi
-    Ws, b, layers = _layers(dev, 1)
     X = torch.randn(64, 256, device=dev)
     d = _cabi.HeadsDesc()
     d.precision, d.P, d.N, d.ldx = 3, 64, 64, 256
@@ -116,75 +70,17 @@ def test_heads_chain_rejects_other_widths_and_bad_arguments(dev):
     assert _cabi.lib().s4g_heads_chain_f32(ctypes.byref(d), st) != 0     # no weights / outputs given
 
 
-def _pre_setup(dev, B, N, N2, seed, with_dense):
-    """Inputs of the feature-propagation tail in front of the heads (s4g_heads_desc_t.pre_*):
-    sparse features (B N2, 256), three neighbour indices + weights per point, an optional dense
-    addend, the first layer's bias, and the two 256 -> 256 layers."""
-    from s4g_release_amd.fused import _Layer
-    g = torch.Generator(device="cpu").manual_seed(seed)
-    r = lambda *s: torch.randn(*s, generator=g)
-    S = (r(B * N2, 256) * torch.tensor([1.0, 25.0, 0.05])[:B, None].repeat_interleave(N2, dim=0)).to(dev)
-    nidx = torch.randint(0, N2, (B * N, 3), generator=g, dtype=torch.int32).to(dev)
-    w = torch.rand(B * N, 3, generator=g)
-    nw = (w / w.sum(dim=1, keepdim=True)).to(dev)
-    dense = (r(B * N, 256) * 0.5).to(dev) if with_dense else None
-    lbias = r(256).to(dev)
-    pl = [_Layer((r(256, 256) / 16).to(dev), r(256).to(dev), 256) for _ in range(2)]
-    return S, nidx, nw, dense, lbias, pl
-
-
-def _pre_reference(S, nidx, nw, dense, lbias, pl, B, N, N2, rnd=lambda t: t.double()):
-    base = (torch.arange(B, device=S.device).repeat_interleave(N) * N2).view(-1, 1)
-    rows = S.double()[(base + nidx.long())]                       # (P, 3, 256)
-    x = (rows * nw.double().unsqueeze(-1)).sum(dim=1) + lbias.double()
-    if dense is not None:
-        x = x + dense.double()
-    x = x.clamp_min(0)
-    for layer in pl:
-        w = layer.W[0] if layer.W.dim() == 3 else layer.W
-        x = (rnd(x.float()) @ rnd(w).t() + layer.bias.double()).clamp_min(0)
-    return x.float()
-
-
 @pytest.mark.parametrize("precision", [3, 2])
 @pytest.mark.parametrize("B,N,N2,with_dense", [(2, 100, 40, False), (3, 171, 64, True), (1, 64, 3, False)])
-def test_heads_chain_with_fp_tail_in_front(dev, precision, B, N, N2, with_dense):
+def test_heads_chain_with_fp_tail_in_front(dev, layer_set, precision, B, N, N2, with_dense):
     """ABI 6: interpolate + add + ReLU in the loader, two 256 -> 256 layers inside LDS, then the
     heads -- against fp64 (f16x2: fp32-class) / a reference rounded to bf16 at the layer inputs."""
-    from s4g_release_amd import _cabi
-    Ws, b, layers = _layers(dev, 11 + N)
-    S, nidx, nw, dense, lbias, pl = _pre_setup(dev, B, N, N2, 5 + N, with_dense)
-    d = _cabi.HeadsDesc()
-    d.precision = precision
-    d.P, d.N = B * N, N
-    d.C, d.H0, d.H1, d.H2, d.H3 = 256, 512, 256, 256, 128
-    pick = (lambda l: l.Wfrag_bf16) if precision == 2 else (lambda l: l.Wfrag)
-    for l, layer in enumerate(layers):
-        d.W_frag[l], d.bias[l], d.w_inv_scale[l] = pick(layer).data_ptr(), layer.bias.data_ptr(), layer.w_inv_scale.data_ptr()
-    for l, layer in enumerate(pl):
-        d.pre_W_frag[l], d.pre_bias[l] = pick(layer).data_ptr(), layer.bias.data_ptr()
-        d.pre_w_inv_scale[l] = layer.w_inv_scale.data_ptr()
-    d.pre_nidx, d.pre_nw, d.pre_sparse, d.pre_N2 = nidx.data_ptr(), nw.data_ptr(), S.data_ptr(), N2
-    d.pre_dense = None if dense is None else dense.data_ptr()
-    d.pre_lbias = lbias.data_ptr()
-    amax = torch.zeros((B, 64), device=dev)
-    amax[:, 9] = S.view(B, -1).abs().amax(dim=1)
-    d.a_amax = amax.data_ptr()
-    if dense is not None:
-        amax2 = torch.zeros((B, 64), device=dev)
-        amax2[:, 1] = dense.view(B, -1).abs().amax(dim=1)
-        d.pre_a_amax2 = amax2.data_ptr()
-    d.a_amax_floor = float(lbias.abs().max())
-    d.rows_per_scene = N
-    outs = [torch.full((B, c, N), float("nan"), device=dev) for c in CH]
-    for h, o in enumerate(outs):
-        d.out[h], d.channels[h] = o.data_ptr(), CH[h]
-    d.sigmoid_head = 3
-    _cabi.check(_cabi.lib().s4g_heads_chain_f32(ctypes.byref(d), torch.cuda.current_stream().cuda_stream), "heads")
-    torch.cuda.synchronize()
+    Ws, b, layers = layer_set(11 + N)
+    S, nidx, nw, dense, lbias, pl = H.pre_setup(dev, B, N, N2, 5 + N, with_dense)
+    outs = H.run(dev, layers, None, B, N, precision, pre=(S, nidx, nw, dense, lbias, pl, N2))
     if precision == 3:
-        X = _pre_reference(S, nidx, nw, dense, lbias, pl, B, N, N2)
-        ref = _reference(Ws, b, X, B, N)
+        X = H.pre_reference(S, nidx, nw, dense, lbias, pl, B, N, N2)
+        ref = H.reference(Ws, b, X, B, N)
         for h in range(4):
             assert torch.isfinite(outs[h]).all()
             err = (outs[h].double() - ref[h]).abs()
@@ -192,8 +88,8 @@ def test_heads_chain_with_fp_tail_in_front(dev, precision, B, N, N2, with_dense)
             assert (err / scale).max().item() < 3e-5, (h, (err / scale).max().item())
     else:
         rb = lambda t: t.to(torch.bfloat16).double()
-        X = _pre_reference(S, nidx, nw, dense, lbias, pl, B, N, N2, rnd=rb)
-        ref = _reference(Ws, b, X, B, N, rnd=rb)
+        X = H.pre_reference(S, nidx, nw, dense, lbias, pl, B, N, N2, rnd=rb)
+        ref = H.reference(Ws, b, X, B, N, rnd=rb)
         for h in range(4):
             scale = max(1.0, ref[h].abs().max().item())
             assert torch.isfinite(outs[h]).all()
