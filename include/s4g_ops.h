@@ -62,7 +62,8 @@ extern "C" {
  *     Added under 14 with no layout change: s4g_eval_frames_f32 / s4g_eval_frames_workspace_bytes (batched antipodal
  *     and collision grading of grasp frames against a labelled scene cloud with normals); s4g_local_search_f32 /
  *     s4g_local_search_workspace_bytes (the data generator's per-frame local grasp search); s4g_darboux_frames_f32 /
- *     s4g_darboux_frames_workspace_bytes (the Darboux frames that search starts from). */
+ *     s4g_darboux_frames_workspace_bytes (the Darboux frames that search starts from); s4g_match_normals_f32 /
+ *     s4g_match_normals_workspace_bytes (the scene normals a view's points take over in front of those frames). */
 #define S4G_ABI_VERSION 14
 
 /* ---------------------------------------------------------------------------
@@ -800,6 +801,49 @@ int s4g_darboux_frames_f32(const float *xyz_b3n, const float *normals_b3n, const
                            const int64_t *frame_count_b, int64_t B, int64_t N, int64_t F, float radius,
                            int32_t min_neighbours, float *frames_bf33, float *points_bf3, int32_t *count_bf,
                            int32_t *flags_bf, void *workspace, size_t workspace_bytes, s4g_stream_t stream);
+
+/* Scene-normal transfer of the data generator's label pipeline (csrc/match_normals.hip):
+ * TorchSingleViewPointCloud._find_normal (data_gen/pcd_classes/torch_single_view_point_cloud.py:135-150) for every
+ * view point of every scene, without host synchronisation.  query (B, 3, N) fp32 the view; scene / scene_normals
+ * (B, 3, M) fp32 the dense scene, the normals used as given; camera (B, 3) fp32 the camera LOCATION, or NULL: no
+ * orientation.  Per view point q of scene b:
+ *   neighbours = every scene point j with squared distance < radius * radius (fp32 product; the subtraction, squares
+ *     and sum in fp32, each op rounded on its own; strict), as for s4g_darboux_frames_f32;
+ *   cap: where more than max_nn qualify, the max_nn smallest by (fp32 squared distance, index) are kept: open3d's
+ *     search_hybrid_vector_3d(radius, max_nn) with its unspecified tie order replaced by "the lower index wins";
+ *   m = the mean of the kept normals, in double: a fixed butterfly over the kept normals in (distance, index) rank
+ *     order, no atomics;
+ *   n = m / |m| (open3d's normalize_normals: a zero vector stays zero);
+ *   orient (camera given; orient_normals_towards_camera_location), ref = camera - q in double: |n| == 0 -> n =
+ *     ref / |ref|, or (0, 0, 1) where ref is zero; else n . ref < 0 -> n = -n; n . ref == 0 leaves n.  A ref that
+ *     is not finite (the query or the camera is not) gives no direction: n stays as it is;
+ *   n is rounded to fp32 once.
+ * Decisions.  (1) No neighbour: the mean of nothing is NaN, which normalize_normals turns into (0, 0, 1); that is then
+ *   oriented; flags bit 1.  (2) The kept normals cancel to exactly zero: the unit vector towards the camera (the zero
+ *   vector without a camera); flags bit 2.  (3) A query that is not finite: nothing compares as near, so (1), and
+ *   flags bit 3; it is not oriented.  (4) A scene point that is not finite is never a neighbour.  (5) A kept normal
+ *   that is not finite: the output is (NaN, NaN, NaN) and flags bit 3 (the reference gives NaN in the components
+ *   concerned, or (0, 0, 1) where the first one is); s4g_darboux_frames_f32 marks such a row degenerate.
+ * Outputs: normals_b3n fp32 (B, 3, N); count_bn int32 (B, N) = the number of normals averaged, at most max_nn;
+ *   flags_bn int32 (B, N): bit 0 = capped (more than max_nn points inside the radius), bit 1 = empty, bit 2 =
+ *   cancelled, bit 3 = not finite.
+ * Neighbour grid: 64^3 toroidal cells of edge just above the radius about the scene's first point, built with the
+ * library's stable radix sort on (scene, cell) keys: NO limit on M.  A scene with a coordinate further than about
+ * 4 000 radii from its first point, or not finite, and a query that far from it, are scanned in index order: the same
+ * neighbour sets, the same ranks, the same bits.  No scene is scanned for its size.
+ * Run-to-run bit-identical and batch invariant (the kept set is a function of the candidate SET, the sum runs in rank
+ * order).  Batches above 256 scenes (fewer where 256 * M >= 2^31) are served in chunks on one workspace.
+ * Cost: the candidates of a query are the population of its 27 cells, read 64 at a time by one wave; each batch that
+ * holds a candidate nearer than the current max_nn-th costs a list insertion, and every 64 insertions one ranking
+ * pass of 128 LDS reads.  A whole scene inside one radius costs M reads per query, as the scan does.
+ * radius in (0, 1e18), max_nn in [1, 64], N and M < 2^30, M >= 1, B <= 65 535 (S4G_EINVAL otherwise).
+ * Workspace: s4g_match_normals_workspace_bytes(B, N, M) bytes (about 36 bytes per scene point and 2 MiB per scene of
+ * a chunk), 256-byte aligned; contents need not be initialised. */
+size_t s4g_match_normals_workspace_bytes(int64_t B, int64_t N, int64_t M);
+int s4g_match_normals_f32(const float *query_b3n, const float *scene_b3m, const float *scene_normals_b3m,
+                          const float *camera_b3 /* may be NULL */, int64_t B, int64_t N, int64_t M, float radius,
+                          int32_t max_nn, float *normals_b3n, int32_t *count_bn, int32_t *flags_bn,
+                          void *workspace, size_t workspace_bytes, s4g_stream_t stream);
 
 /* ---- next row f3: cloud pre-processing on device -------------------------
  * Single-scene passes in front of the network (reference

@@ -30,8 +30,15 @@ def estimate_frames(*args, **kwargs):
     return _estimate(*args, **kwargs)
 
 
+def match_normals(*args, **kwargs):
+    """The data generator's normal matching: every view point takes the mean normal of its nearest dense-scene points,
+    for every scene in one call.  See `postprocess.match_normals`."""
+    from .postprocess import match_normals as _match
+    return _match(*args, **kwargs)
+
+
 def label_view(*args, **kwargs):
-    """View cloud with normals in, S4G labels out: the sampled indices, `estimate_frames` and `grade_local_search` in
-    one call.  See `postprocess.label_view`."""
+    """View cloud in, S4G labels out: `match_normals` where asked for, the sampled indices, `estimate_frames` and
+    `grade_local_search` in one call.  See `postprocess.label_view`."""
     from .postprocess import label_view as _label
     return _label(*args, **kwargs)

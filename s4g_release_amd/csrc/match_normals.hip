@@ -1,0 +1,366 @@
+// Scene-normal transfer of the data generator's label pipeline for every view point of every scene:
+// TorchSingleViewPointCloud._find_normal (data_gen/pcd_classes/torch_single_view_point_cloud.py:135-150), which loops
+// over the view with one kd-tree search_hybrid_vector_3d(radius, max_nn) each, then normalises and orients the cloud.
+// Contract: include/s4g_ops.h (s4g_match_normals_f32).
+//
+// Neighbourhood: a toroidal 64^3 cell grid over the SCENE (the keys; the queries are another set) with the cell edge
+// just above the radius and the cell coordinates of grid.h, built with the library's own stable radix sort instead of
+// the LDS bitmaps of the 32^3 grid -- so there is no limit on the number of scene points.  One sort of
+// (scene << 18 | cell, point index) pairs serves up to MN_CHUNK scenes; being stable it leaves every cell in ascending
+// point index.  The cell starts are an exclusive scan of the cells' populations (integer atomics: the counts do not
+// depend on their order).  A compact copy holds the records (x, y, z, index) in sorted order.  A batch above MN_CHUNK
+// scenes is served chunk after chunk on the same workspace.
+//
+// Per view point, one wave: the candidates of the 27 cells (nine rows of three x-adjacent cells: one run of records
+// each, two where the row wraps), 64 at a time; a candidate inside the radius is the 64-bit key (fp32 bits of d^2,
+// scene index) -- non-negative floats order as their bit patterns, the index makes every key distinct.  The wave
+// keeps a list of at most 128 keys in LDS and a threshold, the max_nn-th smallest key seen so far: a batch is
+// filtered against it by ballot, the survivors are appended, and a full list is cut back to its max_nn smallest by
+// ranking every key against the list.  The kept set depends on the candidates as a SET only, so the grid and the
+// index-order scan (a scene or a query outside the grid's exactness range) give the same keys in the same rank order.
+// The kept normals are then summed in double by a fixed butterfly over the ranks: no atomics touch a sum, the order
+// depends on the scene and the query alone -- run-to-run bit-identical and batch invariant, and identical between
+// the grid and the scan.
+#include "grid.h"
+#include "radix_sort.h"
+
+namespace s4g {
+
+constexpr int MN_DIM = 64;                                 // cells per axis (toroidal)
+constexpr int MN_CELL_BITS = 18;
+constexpr int MN_CELLS = MN_DIM * MN_DIM * MN_DIM;         // 262 144
+constexpr int MN_CHUNK = 256;                              // scenes per sort: 8 more key bits
+constexpr int MN_MAX_NN = 64;
+constexpr int MN_LIST = 128;                               // keys a wave buffers between two cuts
+constexpr int MN_THREADS = 256, MN_WAVES = MN_THREADS / 64;
+constexpr int MN_BUILD_THREADS = 256;
+
+struct MatchWs {
+  uint32_t *keys_a, *keys_b, *vals_a, *vals_b;   // [Bc * M] sort ping-pong; keys_b / vals_b hold the result
+  void* sort;                                    // radix_sort_ws_bytes(Bc * M)
+  int* count;                                    // [Bc * MN_CELLS + 1] cell populations (the last entry stays 0) ...
+  int* flags;                                    // ... then [Bc] 1 = scene out of the exactness range -> scan (cleared together)
+  int* start;                                    // [Bc * MN_CELLS + 1] record offsets, scene after scene
+  void* scan;                                    // scan_ws_bytes(Bc * MN_CELLS + 1)
+  float4* rec;                                   // [Bc * M] (x, y, z, index bits) in sorted order
+};
+
+static size_t mn_align(size_t v) { return (v + 255) & ~(size_t)255; }
+
+// scenes one pass serves: the sort's keys hold 32 bits and the scan's offsets 31
+static int64_t mn_chunk(int64_t B, int64_t M) {
+  int64_t c = ((1ll << 31) - 1) / (M > 0 ? M : 1);
+  if (c > MN_CHUNK) c = MN_CHUNK;
+  if (c > B) c = B;
+  return c < 1 ? 1 : c;
+}
+
+// 16-byte words that hold the populations of Bc scenes, the closing entry and the scene flags
+static size_t mn_clear_int4(int64_t Bc) { return ((size_t)Bc * MN_CELLS + 1 + (size_t)Bc + 3) / 4; }
+
+static size_t match_ws(void* base, int64_t Bc, int64_t M, MatchWs* w) {
+  char* p = (char*)base;
+  size_t off = 0;
+  auto take = [&](size_t bytes) {
+    char* r = p ? p + off : nullptr;
+    off += mn_align(bytes);
+    return r;
+  };
+  const size_t n = (size_t)Bc * (size_t)M, cells = (size_t)Bc * MN_CELLS + 1;
+  uint32_t* ka = (uint32_t*)take(n * 4);
+  uint32_t* kb = (uint32_t*)take(n * 4);
+  uint32_t* va = (uint32_t*)take(n * 4);
+  uint32_t* vb = (uint32_t*)take(n * 4);
+  void* sort = take(radix_sort_ws_bytes(n));
+  int* count = (int*)take(mn_clear_int4(Bc) * sizeof(int4));
+  int* start = (int*)take(cells * 4);
+  void* scan = take(scan_ws_bytes(cells));
+  float4* rec = (float4*)take(n * sizeof(float4));
+  if (w && p) {
+    w->keys_a = ka; w->keys_b = kb; w->vals_a = va; w->vals_b = vb;
+    w->sort = sort;
+    w->count = count;
+    w->flags = count + cells;
+    w->start = start;
+    w->scan = scan;
+    w->rec = rec;
+  }
+  return off;
+}
+
+__device__ __forceinline__ int mn_cell(int cx, int cy, int cz) {
+  return ((cz & (MN_DIM - 1)) << 12) | ((cy & (MN_DIM - 1)) << 6) | (cx & (MN_DIM - 1));
+}
+
+// Clears the cell populations and the scene flags (a kernel of the call's own, so that a captured graph holds a plain
+// chain of kernel nodes).
+__global__ __launch_bounds__(MN_BUILD_THREADS) void match_clear_kernel(int4* __restrict__ p, size_t n4) {
+  const size_t i = (size_t)blockIdx.x * MN_BUILD_THREADS + threadIdx.x;
+  if (i < n4) p[i] = make_int4(0, 0, 0, 0);
+}
+
+// One thread per scene point: its sort key and its cell's population.  A point outside the exactness range of
+// grid.h (or not finite) sends its scene to the scan; it still gets a key (cell 0) so that the sort stays whole.
+__global__ __launch_bounds__(MN_BUILD_THREADS) void match_keys_kernel(const float* __restrict__ scene, int M,
+                                                                      float inv_h, MatchWs ws) {
+  const int b = blockIdx.y;
+  const int j = blockIdx.x * MN_BUILD_THREADS + threadIdx.x;
+  if (j >= M) return;
+  const float* __restrict__ p0 = scene + (size_t)b * 3 * M;
+  const float ox = p0[0], oy = p0[M], oz = p0[2 * (size_t)M];
+  const float x = p0[j], y = p0[M + j], z = p0[2 * (size_t)M + j];
+  int cell = 0;
+  if (grid_coord_ok(x, ox, inv_h) && grid_coord_ok(y, oy, inv_h) && grid_coord_ok(z, oz, inv_h))
+    cell = mn_cell(grid_coord(x, ox, inv_h), grid_coord(y, oy, inv_h), grid_coord(z, oz, inv_h));
+  else
+    ws.flags[b] = 1;
+  const size_t i = (size_t)b * M + j;
+  ws.keys_a[i] = ((uint32_t)b << MN_CELL_BITS) | (uint32_t)cell;
+  ws.vals_a[i] = (uint32_t)j;
+  atomicAdd(&ws.count[(size_t)b * MN_CELLS + cell], 1);
+}
+
+// One thread per sorted record: the compact copy the queries read.
+__global__ __launch_bounds__(MN_BUILD_THREADS) void match_order_kernel(const float* __restrict__ scene, int M,
+                                                                       MatchWs ws) {
+  const int b = blockIdx.y;
+  const int q = blockIdx.x * MN_BUILD_THREADS + threadIdx.x;
+  if (q >= M) return;
+  const size_t i = (size_t)b * M + q;
+  const uint32_t j = ws.vals_b[i];
+  if (j >= (uint32_t)M) return;   // (cannot happen: the values are the build's own)
+  const float* __restrict__ p0 = scene + (size_t)b * 3 * M;
+  ws.rec[i] = make_float4(p0[j], p0[M + j], p0[2 * (size_t)M + j], __int_as_float((int)j));
+}
+
+__device__ __forceinline__ bool mn_finite(float v) { return fabsf(v) <= 3.402823466e38f; }
+__device__ __forceinline__ bool mn_finite(double v) { return fabs(v) <= 1.7976931348623157e308; }
+
+// A wave's running selection: `list` holds n distinct keys, every one below `thr`; once max_nn keys have been seen
+// thr is the max_nn-th smallest of them, so a key at or above it can never be kept.
+struct MnSelect {
+  volatile uint64_t* list;   // [MN_LIST] LDS, this wave's
+  uint64_t thr;
+  int n, inside, max_nn, lane;
+
+  // cuts the list to its min(n, max_nn) smallest keys, in ascending order
+  __device__ __forceinline__ void cut() {
+    const uint64_t none = ~0ull;
+    const uint64_t k0 = lane < n ? list[lane] : none, k1 = lane + 64 < n ? list[lane + 64] : none;
+    int r0 = 0, r1 = 0;
+    for (int i = 0; i < n; ++i) {
+      const uint64_t v = list[i];
+      r0 += v < k0 ? 1 : 0;
+      r1 += v < k1 ? 1 : 0;
+    }
+    __builtin_amdgcn_wave_barrier();
+    if (lane < n && r0 < max_nn) list[r0] = k0;
+    if (lane + 64 < n && r1 < max_nn) list[r1] = k1;
+    __builtin_amdgcn_wave_barrier();
+    if (n >= max_nn) {
+      n = max_nn;
+      thr = list[max_nn - 1];
+    }
+  }
+
+  // one candidate per lane (wave-uniform call)
+  __device__ __forceinline__ void consider(bool valid, float d2, float r2, int index) {
+    const bool in = valid && d2 < r2;
+    inside += __popcll(__ballot(in));
+    const uint64_t key = ((uint64_t)__float_as_uint(d2) << 32) | (uint32_t)index;
+    const bool keep = in && key < thr;
+    const uint64_t m = __ballot(keep);
+    if (m == 0) return;
+    const int cnt = __popcll(m);
+    if (n + cnt > MN_LIST) cut();   // n <= 64 afterwards
+    if (keep) list[n + mask_rank(m)] = key;
+    n += cnt;
+    __builtin_amdgcn_wave_barrier();
+  }
+};
+
+__device__ __forceinline__ double mn_wave_sum(double v) {
+#pragma unroll
+  for (int off = 1; off < 64; off <<= 1) v += __shfl_xor(v, off);
+  return v;
+}
+
+__global__ __launch_bounds__(MN_THREADS) void match_query_kernel(
+    const float* __restrict__ query, const float* __restrict__ scene, const float* __restrict__ scene_normals,
+    const float* __restrict__ camera, int N, int M, float r2, float inv_h, int max_nn, MatchWs ws,
+    float* __restrict__ normals, int32_t* __restrict__ count, int32_t* __restrict__ flags) {
+  __shared__ uint64_t lists[MN_WAVES][MN_LIST];
+  const int b = blockIdx.y;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int q = blockIdx.x * MN_WAVES + wave;
+  if (q >= N) return;   // the whole wave
+  const float* __restrict__ q0 = query + (size_t)b * 3 * N;
+  const float* __restrict__ p0 = scene + (size_t)b * 3 * M;
+  const float* __restrict__ n0 = scene_normals + (size_t)b * 3 * M;
+  const float x = q0[q], y = q0[N + q], z = q0[2 * (size_t)N + q];
+  const bool q_ok = mn_finite(x) && mn_finite(y) && mn_finite(z);
+  MnSelect s;
+  s.list = lists[wave];
+  s.thr = ~0ull;
+  s.n = 0;
+  s.inside = 0;
+  s.max_nn = max_nn;
+  s.lane = lane;
+  if (q_ok) {   // nothing is near a point that is not finite
+    const float ox = p0[0], oy = p0[M], oz = p0[2 * (size_t)M];
+    const bool grid = ws.flags[b] == 0 && grid_coord_ok(x, ox, inv_h) && grid_coord_ok(y, oy, inv_h) &&
+                      grid_coord_ok(z, oz, inv_h);
+    if (grid) {
+      const int icx = grid_coord(x, ox, inv_h), icy = grid_coord(y, oy, inv_h), icz = grid_coord(z, oz, inv_h);
+      const int* __restrict__ start = ws.start + (size_t)b * MN_CELLS;
+      // lane r < 9 fetches row r's runs: the row's three x cells are one run of records, or two where it wraps
+      int vb0 = 0, ve0 = 0, vb1 = 0, ve1 = 0;
+      if (lane < 9) {
+        const int dz = lane / 3 - 1, dy = lane % 3 - 1;
+        const int row = mn_cell(0, icy + dy, icz + dz);
+        const int x0 = (icx - 1) & (MN_DIM - 1);
+        vb0 = start[row + x0];
+        if (x0 <= MN_DIM - 3) {
+          ve0 = start[row + x0 + 3];
+        } else {
+          ve0 = start[row + MN_DIM];
+          vb1 = start[row];
+          ve1 = start[row + ((x0 + 3) & (MN_DIM - 1))];
+        }
+      }
+      const float4* __restrict__ rec = ws.rec;   // the starts are offsets into the whole chunk
+      const int lo = b * M, hi = lo + M;         // (the runs of scene b lie inside its own records)
+      for (int r = 0; r < 9; ++r) {
+        for (int run = 0; run < 2; ++run) {
+          int rb = __shfl(run ? vb1 : vb0, r), re = __shfl(run ? ve1 : ve0, r);
+          rb = rb < lo ? lo : rb;
+          re = re > hi ? hi : re;
+          for (int base = rb; base < re; base += 64) {
+            const int i = base + lane;
+            const bool valid = i < re;
+            float4 c = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (valid) c = rec[i];
+            s.consider(valid, dist2<false>(x, y, z, c.x, c.y, c.z), r2, __float_as_int(c.w));
+          }
+        }
+      }
+    } else {
+      for (int base = 0; base < M; base += 64) {
+        const int j = base + lane;
+        const bool valid = j < M;
+        float cx = 0.f, cy = 0.f, cz = 0.f;
+        if (valid) { cx = p0[j]; cy = p0[M + j]; cz = p0[2 * (size_t)M + j]; }
+        s.consider(valid, dist2<false>(x, y, z, cx, cy, cz), r2, j);
+      }
+    }
+  }
+  s.cut();   // ascending, at most max_nn
+  const int k = s.n < max_nn ? s.n : max_nn;
+  // the kept normals, rank r in lane r, summed in double by a fixed butterfly
+  double ax = 0.0, ay = 0.0, az = 0.0;
+  bool bad = false;
+  if (lane < k) {
+    const uint32_t j = (uint32_t)s.list[lane];
+    if (j < (uint32_t)M) {   // (cannot be otherwise: the index is the scene's own)
+      const float fx = n0[j], fy = n0[M + j], fz = n0[2 * (size_t)M + j];
+      bad = !(mn_finite(fx) && mn_finite(fy) && mn_finite(fz));
+      ax = (double)fx; ay = (double)fy; az = (double)fz;
+    }
+  }
+  const bool any_bad = __ballot(bad) != 0;
+  const double sx = mn_wave_sum(ax), sy = mn_wave_sum(ay), sz = mn_wave_sum(az);
+  if (lane != 0) return;
+  int flag = (s.inside > max_nn ? 1 : 0) | (k == 0 ? 2 : 0) | (!q_ok || any_bad ? 8 : 0);
+  double nx = 0.0, ny = 0.0, nz = 1.0;   // the mean of nothing is NaN: normalize_normals makes it (0, 0, 1)
+  bool orient = camera != nullptr;
+  if (any_bad) {
+    nx = ny = nz = __longlong_as_double(0x7ff8000000000000ll);
+    orient = false;
+  } else if (k > 0) {
+    const double mx = sx / (double)k, my = sy / (double)k, mz = sz / (double)k;
+    const double len = sqrt(mx * mx + my * my + mz * mz);
+    if (len > 0.0) {
+      nx = mx / len; ny = my / len; nz = mz / len;
+    } else {
+      nx = ny = nz = 0.0;   // the kept normals cancel
+      flag |= 4;
+    }
+  }
+  if (orient) {
+    const float* __restrict__ c0 = camera + (size_t)b * 3;
+    const double rx = (double)c0[0] - (double)x, ry = (double)c0[1] - (double)y, rz = (double)c0[2] - (double)z;
+    if (mn_finite(rx) && mn_finite(ry) && mn_finite(rz)) {   // no reference direction otherwise: n stays
+      if (nx == 0.0 && ny == 0.0 && nz == 0.0) {
+        const double rl = sqrt(rx * rx + ry * ry + rz * rz);   // differences of fp32 numbers: no overflow in double
+        if (rl > 0.0) {
+          nx = rx / rl; ny = ry / rl; nz = rz / rl;
+        } else {
+          nz = 1.0;
+        }
+      } else if (nx * rx + ny * ry + nz * rz < 0.0) {
+        nx = -nx; ny = -ny; nz = -nz;
+      }
+    }
+  }
+  float* __restrict__ o = normals + (size_t)b * 3 * N;
+  o[q] = (float)nx;
+  o[N + q] = (float)ny;
+  o[2 * (size_t)N + q] = (float)nz;
+  count[(size_t)b * N + q] = k;
+  flags[(size_t)b * N + q] = flag;
+}
+
+}  // namespace s4g
+
+extern "C" size_t s4g_match_normals_workspace_bytes(int64_t B, int64_t N, int64_t M) {
+  (void)N;
+  if (B <= 0 || M <= 0 || M >= (1ll << 30)) return 0;
+  return s4g::match_ws(nullptr, s4g::mn_chunk(B, M), M, nullptr);
+}
+
+extern "C" int s4g_match_normals_f32(const float* query_b3n, const float* scene_b3m, const float* scene_normals_b3m,
+                                     const float* camera_b3, int64_t B, int64_t N, int64_t M, float radius,
+                                     int32_t max_nn, float* normals_b3n, int32_t* count_bn, int32_t* flags_bn,
+                                     void* workspace, size_t workspace_bytes, s4g_stream_t stream) {
+  using namespace s4g;
+  if (B < 0 || B > 65535 || N < 0 || N >= (1ll << 30) || M < 1 || M >= (1ll << 30)) return S4G_EINVAL;
+  if (!(radius > 0.f) || !(radius < 1e18f) || max_nn < 1 || max_nn > MN_MAX_NN) return S4G_EINVAL;
+  if (B == 0 || N == 0) return S4G_OK;
+  if (!query_b3n || !scene_b3m || !scene_normals_b3m || !normals_b3n || !count_bn || !flags_bn) return S4G_EINVAL;
+  hipStream_t st = (hipStream_t)stream;
+  const float r2 = radius * radius;   // fp32 product, as for the ball query
+  // cell edge slightly above the radius, as for the ball query (grid.h)
+  const float h = radius * (1.0f + 1.0f / 256.0f);
+  const float inv_h = 1.0f / h;
+  const int64_t chunk = mn_chunk(B, M);
+  const size_t need = match_ws(nullptr, chunk, M, nullptr);
+  if (!workspace || workspace_bytes < need) return S4G_EWORKSPACE;
+  for (int64_t b0 = 0; b0 < B; b0 += chunk) {
+    const int64_t Bc = B - b0 < chunk ? B - b0 : chunk;
+    MatchWs w = {};
+    match_ws(workspace, Bc, M, &w);
+    const size_t n = (size_t)Bc * (size_t)M, cells = (size_t)Bc * MN_CELLS + 1;
+    const float* sc = scene_b3m + (size_t)b0 * 3 * M;
+    const size_t n4 = mn_clear_int4(Bc);
+    hipLaunchKernelGGL(match_clear_kernel, dim3((unsigned)((n4 + MN_BUILD_THREADS - 1) / MN_BUILD_THREADS)),
+                       dim3(MN_BUILD_THREADS), 0, st, (int4*)w.count, n4);
+    S4G_LAUNCH_CHECK();
+    const dim3 bgrid((unsigned)((M + MN_BUILD_THREADS - 1) / MN_BUILD_THREADS), (unsigned)Bc);
+    hipLaunchKernelGGL(match_keys_kernel, bgrid, dim3(MN_BUILD_THREADS), 0, st, sc, (int)M, inv_h, w);
+    S4G_LAUNCH_CHECK();
+    unsigned bits = MN_CELL_BITS;
+    while (bits < 32 && ((int64_t)1 << (bits - MN_CELL_BITS)) < Bc) ++bits;
+    if (int rc = radix_sort_pairs(w.sort, radix_sort_ws_bytes(n), w.keys_a, w.keys_b, w.vals_a, w.vals_b, n, bits, st))
+      return rc;
+    if (int rc = exclusive_scan_i32(w.scan, scan_ws_bytes(cells), w.count, w.start, cells, st)) return rc;
+    hipLaunchKernelGGL(match_order_kernel, bgrid, dim3(MN_BUILD_THREADS), 0, st, sc, (int)M, w);
+    S4G_LAUNCH_CHECK();
+    hipLaunchKernelGGL(match_query_kernel, dim3((unsigned)((N + MN_WAVES - 1) / MN_WAVES), (unsigned)Bc),
+                       dim3(MN_THREADS), 0, st, query_b3n + (size_t)b0 * 3 * N, sc,
+                       scene_normals_b3m + (size_t)b0 * 3 * M, camera_b3 ? camera_b3 + (size_t)b0 * 3 : nullptr, (int)N,
+                       (int)M, r2, inv_h, (int)max_nn, w, normals_b3n + (size_t)b0 * 3 * N, count_bn + (size_t)b0 * N,
+                       flags_bn + (size_t)b0 * N);
+    S4G_LAUNCH_CHECK();
+  }
+  return S4G_OK;
+}

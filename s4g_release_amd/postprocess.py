@@ -797,27 +797,127 @@ def map_cloud_index(valid_index, frame_index):
     return torch.where(live, got, got.new_full((), -1))
 
 
+NORMAL_MAX_NN = 30                         # data_gen/configs/config.py:31
+
+
+@dataclass
+class MatchedNormals:
+    """What `match_normals` returns: device tensors, one column per view point.  `normals` (B, 3, N) fp32, `count`
+    (B, N) int32 the number of scene normals averaged (at most max_nn), `flags` (B, N) int32 the kernel's own (bit 0 =
+    capped, bit 1 = empty, bit 2 = cancelled, bit 3 = not finite)."""
+    normals: torch.Tensor
+    count: torch.Tensor
+    flags: torch.Tensor
+    unbatched: bool = False
+
+    capped = property(lambda self: (self.flags & 1) != 0)
+    empty = property(lambda self: (self.flags & 2) != 0)
+    cancelled = property(lambda self: (self.flags & 4) != 0)
+    nonfinite = property(lambda self: (self.flags & 8) != 0)
+
+
+def match_normals(cloud, scene_points, scene_normals, camera=None, radius=CURVATURE_RADIUS, max_nn=NORMAL_MAX_NN):
+    """The data generator's normal matching -- `TorchSingleViewPointCloud._find_normal`
+    (data_gen/pcd_classes/torch_single_view_point_cloud.py:135-150), which loops over the view with one kd-tree
+    `search_hybrid_vector_3d(radius, max_nn)` each and then normalises and orients the cloud -- for every view point of
+    every scene in one sync-free, graph-capturable call -> `MatchedNormals`, whose `normals` are `estimate_frames`'
+    and `label_view`'s input.
+
+    cloud (B, 3, N) fp32 the view; scene_points, scene_normals (B, 3, M) fp32 the dense scene, the normals used as
+    given; camera (B, 3) or (3,) (one location for every scene) the camera location `camera_pose[0:3, 3]`, None: no
+    orientation.  One view may be passed unbatched -- cloud (3, N), with its scene (3, M) if that is unbatched too --
+    and gets a leading 1: the result is ALWAYS batched (`unbatched` set, as `estimate_frames` does).  Per view point:
+    the scene points with squared distance < radius^2 (fp32, strict), of them the max_nn smallest by (fp32 squared
+    distance, index) -- open3d's hybrid search with the tie order pinned: the lower index wins -- the mean of their
+    normals in double, normalised, turned towards the camera, rounded to fp32 once.  No limit on M: the neighbour grid
+    is built with the library's radix sort.
+
+    Decisions.  (1) No scene point in the radius: (0, 0, 1), which open3d makes of numpy's NaN mean, then oriented;
+    `empty`.  (2) The kept normals cancel to exactly zero: the unit vector towards the camera (zero without a camera);
+    `cancelled`.  (3) A view point that is not finite: as (1), not oriented, and `nonfinite`.  (4) A scene point that
+    is not finite is never a neighbour.  (5) A kept normal that is not finite: NaN, and `nonfinite`; `estimate_frames`
+    then marks the row degenerate."""
+    for name, t in (("cloud", cloud), ("scene_points", scene_points), ("scene_normals", scene_normals)):
+        if not isinstance(t, torch.Tensor) or t.device.type != "cuda":
+            raise RuntimeError("%s must be a CUDA tensor (there is no CPU fallback)" % name)
+    if not float(radius) > 0.0:
+        raise ValueError("radius must be positive, got %r" % (radius,))
+    if not 1 <= int(max_nn) <= 64:
+        raise ValueError("max_nn must be in [1, 64], got %r" % (max_nn,))
+    if camera is not None and (not isinstance(camera, torch.Tensor) or camera.device.type != "cuda"):
+        raise RuntimeError("camera must be a CUDA tensor (there is no CPU fallback)")
+    unbatched = cloud.dim() == 2
+    if unbatched:                       # one view: (3, N); its scene (3, M) gets the leading 1 too, a (1, ...) scene passes
+        cloud = cloud[None]
+        if scene_points.dim() == 2:
+            scene_points, scene_normals = scene_points[None], scene_normals[None]
+    xyz = _F._f32c(cloud, "cloud")
+    pts = _F._f32c(scene_points, "scene_points")
+    nrm = _F._f32c(scene_normals, "scene_normals")
+    if xyz.dim() != 3 or xyz.size(1) != 3:
+        raise RuntimeError("cloud must be (B, 3, N)")
+    B, _, N = xyz.shape
+    if pts.dim() != 3 or pts.size(0) != B or pts.size(1) != 3 or pts.size(2) < 1:
+        raise RuntimeError("scene_points must be (B, 3, M) with M >= 1")
+    M = pts.size(2)
+    if tuple(nrm.shape) != (B, 3, M):
+        raise RuntimeError("scene_normals must be (B, 3, M) like scene_points")
+    cam = None
+    if camera is not None:
+        cam = _F._f32c(camera, "camera")
+        if cam.dim() == 1 and cam.numel() == 3:
+            cam = cam.view(1, 3).expand(B, 3)
+        if tuple(cam.shape) != (B, 3):
+            raise RuntimeError("camera must be (B, 3) or (3,)")
+        cam = cam.contiguous()
+    if len({xyz.device, pts.device, nrm.device} | ({cam.device} if cam is not None else set())) != 1:
+        raise RuntimeError("cloud, scene_points, scene_normals and camera must live on one device")
+    dev = xyz.device
+    normals = torch.empty((B, 3, N), dtype=torch.float32, device=dev)
+    count = torch.empty((B, N), dtype=torch.int32, device=dev)
+    flags = torch.empty((B, N), dtype=torch.int32, device=dev)
+    nbytes = _cabi.lib().s4g_match_normals_workspace_bytes(B, N, M)
+    ws = torch.empty((max(int(nbytes), 1),), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        rc = _cabi.lib().s4g_match_normals_f32(xyz.data_ptr(), pts.data_ptr(), nrm.data_ptr(),
+                                               None if cam is None else cam.data_ptr(), B, N, M, float(radius),
+                                               int(max_nn), normals.data_ptr(), count.data_ptr(), flags.data_ptr(),
+                                               ws.data_ptr(), int(nbytes), _F._stream())
+    _cabi.check(rc, "match_normals")
+    return MatchedNormals(normals, count, flags, unbatched)
+
+
 @dataclass
 class ViewLabels:
     """What `label_view` returns: the `LocalSearch` of the view's frames, the `DarbouxFrames` they came from and
-    `cloud_index` (B, F): the cloud indices of the valid frames in ascending order, then -1 (`search.count` of them)."""
+    `cloud_index` (B, F): the cloud indices of the valid frames in ascending order, then -1 (`search.count` of them);
+    `matched`: the `MatchedNormals` the frames were estimated on, None unless `match_normal` was asked for."""
     search: LocalSearch
     darboux: DarbouxFrames
     cloud_index: torch.Tensor
+    matched: MatchedNormals = None
 
 
 def label_view(cloud, normals, scene_points, scene_normals, scene_labels, config=None, frame_index=None,
-               frame_count=None, radius=CURVATURE_RADIUS, min_neighbours=5):
-    """`TorchSingleViewPointCloud.run_score(scene, match_normal=False)` (:182-201): view cloud with normals in, S4G
-    labels out, in one sync-free call -- the sampled indices (:53, z > config.table_height + 0.015, unless frame_index
-    is given), `estimate_frames`, then `grade_local_search` on its points and frames with its frame count ->
-    `ViewLabels`.  cloud, normals (B, 3, N) are the view; scene_points, scene_normals (B, 3, M) and scene_labels
-    (B, M) the dense scene the placements are graded against (the view itself in the reference's eval mode).  One
-    unbatched view (3, N) gets a leading 1, with its scene if that is unbatched too; the results are always batched."""
+               frame_count=None, radius=CURVATURE_RADIUS, min_neighbours=5, match_normal=False, camera=None,
+               max_nn=NORMAL_MAX_NN):
+    """`TorchSingleViewPointCloud.run_score(scene, match_normal)` (:182-201): view cloud in, S4G labels out, in one
+    sync-free call -- `match_normals` where match_normal is set (:189-190), the sampled indices (:53, z >
+    config.table_height + 0.015, unless frame_index is given), `estimate_frames`, then `grade_local_search` on its
+    points and frames with its frame count -> `ViewLabels`.  cloud, normals (B, 3, N) are the view; scene_points,
+    scene_normals (B, 3, M) and scene_labels (B, M) the dense scene the placements are graded against (the view itself
+    in the reference's eval mode).  One unbatched view (3, N) gets a leading 1, with its scene if that is unbatched
+    too; the results are always batched.  match_normal=True: `normals` may be None; the view's normals are
+    `match_normals(cloud, scene_points, scene_normals, camera, radius, max_nn).normals` (camera (B, 3) or (3,): the
+    camera location) and `ViewLabels.matched` holds that result."""
     cfg = config or LocalSearchConfig()
+    matched = None
+    if match_normal:
+        matched = match_normals(cloud, scene_points, scene_normals, camera, radius, max_nn)
+        normals = matched.normals[0] if isinstance(cloud, torch.Tensor) and cloud.dim() == 2 else matched.normals
     d = estimate_frames(cloud, normals, frame_index, frame_count, radius, min_neighbours,
                         sample_region=cfg.table_height + SAMPLE_REGION_OFFSET)
     if d.unbatched and scene_points.dim() == 2:          # one view against one unbatched scene; a (1, ...) scene passes as is
         scene_points, scene_normals, scene_labels = scene_points[None], scene_normals[None], scene_labels[None]
     s = grade_local_search(d.points, d.frames, scene_points, scene_normals, scene_labels, cfg, d.frame_count)
-    return ViewLabels(s, d, map_cloud_index(s.valid_index, d.frame_index))
+    return ViewLabels(s, d, map_cloud_index(s.valid_index, d.frame_index), matched)
