@@ -396,14 +396,18 @@ typedef struct s4g_gemm_desc {
    * ignored) -- the reduced-precision roofline configuration.
    * ABI >= 3, optional: a SECOND layer fused behind this one (S4G_GEMM_F16X2, loader PLAIN
    * GATHER_MLP1, GATHER_ADD or INTERP_ADD, Kpad16 == Cout == C with C = 128, 256 or 512 -- for the plain
-   * loader + STORE also Kpad16 == 2 C == 512: the first layer then runs through two panel loads
-   * --, Cout2 % 64 == 0; epilogue MAX
+   * loader + STORE at C == 256 also Kpad16 == 2 C or 4 C: the first layer then runs through two or four
+   * panel loads --, Cout2 % 64 == 0; epilogue MAX
    * with K == 64 and groups == 1, or STORE with any group count -- W2 / w2_inv_scale / bias2
    * then hold `groups` blocks like their first-layer counterparts): the launch computes
    *   out = epilogue(relu2(bias2 + W2 . relu(bias + W . A)))
    * with the C-channel intermediate kept in LDS (split with a per-tile power-of-two scale).
    * W2_f16x2_frag / w2_inv_scale / bias2 describe W2 (Cout2 x C) like W_f16x2_frag /
-   * w_inv_scale / bias describe W; out, ldc, c_coff, out_amax refer to the final output. */
+   * w_inv_scale / bias describe W; out, ldc, c_coff, out_amax refer to the final output.
+   * S4G_GEMM_BF16 chains with epilogue MAX need a ReLU behind the LAST layer (relu2, or relu3 of a three-layer
+   * chain): the single-plane form only has the max of activated values and answers S4G_EUNSUPPORTED
+   * otherwise.  The F16X2 form takes MAX with or without it.  s4g_gemm_chain_supported answers for exactly
+   * the (loader, epilogue, C, Kpad16) combinations this paragraph accepts. */
   const void *W2_f16x2_frag;
   const float *w2_inv_scale;
   const float *bias2;

@@ -2150,9 +2150,9 @@ extern "C" int s4g_mlp_gemm_f32(const s4g_gemm_desc_t* d, s4g_stream_t stream) {
   if (d->W2_f16x2_frag) {
     // two fused layers: K = C -> C -> Cout2 with C = 128 (128 positions per workgroup) or
     // C = 256 (64 positions), epilogue MAX (K == 64 neighbours) or STORE
-    // layer 1 may be one or two panels deep (Kpad16 = C or 2 C)
+    // layer 1 may be one, two or four panels deep (Kpad16 = C, 2 C or 4 C; the list below says for which loaders)
     const bool c128 = d->Cout == 128 && d->Kpad16 == 128,
-               c256 = d->Cout == 256 && (d->Kpad16 == 256 || d->Kpad16 == 512),
+               c256 = d->Cout == 256 && (d->Kpad16 == 256 || d->Kpad16 == 512 || d->Kpad16 == 1024),
                c512 = d->Cout == 512 && d->Kpad16 == 512;
     const bool store = d->epilogue == S4G_GEMM_EPI_STORE;
     const bool bf1 = d->precision == S4G_GEMM_BF16;   // one bf16 plane, one product, no scales
@@ -2163,6 +2163,9 @@ extern "C" int s4g_mlp_gemm_f32(const s4g_gemm_desc_t* d, s4g_stream_t stream) {
         (h2 && !d->w2_inv_scale) || !d->bias2 ||
         (store && (((d->ldc | d->c_coff | d->c_gcol) & 3) || ((uintptr_t)d->out & 15))))
       return S4G_EINVAL;
+    // the single-plane form's waves own four row blocks and its final phase has the max of ACTIVATED values only (the
+    // generic max epilogue takes two): without a ReLU behind the last layer it would write nothing
+    if (bf1 && !store && !(d->W3_f16x2_frag ? d->relu3 : d->relu2)) return S4G_EUNSUPPORTED;
     // the xyz-only first layer of an SA level on pre-gathered records: as one MFMA step inside the chain kernel
     // (f16x2 form; S4G_MLP1_MFMA=0, read per launch: the vector-ALU loader, for tests and A/B runs)
     if (h2 && d->loader == S4G_GEMM_LOAD_GATHER_MLP1 && d->rel_xyz4 && d->epilogue == S4G_GEMM_EPI_MAX &&

@@ -12,6 +12,7 @@ import pytest
 import torch
 
 from tests import golden_util as GU
+from tests.chain_ref import bf16_frag as _frag    # shared with the chain edge suite
 
 pytestmark = pytest.mark.gpu
 HEADS = ("score", "frame_R", "frame_t", "movable_logits")
@@ -31,13 +32,6 @@ def _run(desc_kwargs):
 
 def _bf(x):
     return x.to(torch.bfloat16).double()
-
-
-def _frag(w):
-    """(G, Cout, K16) or (Cout, K16) fp32 -> bf16 fragment-ordered plane + the bf16x3 planes."""
-    from s4g_release_amd.fused import fragment_order, split_bf16x3
-    w3 = split_bf16x3(w)
-    return fragment_order(w3[:1])[:, :, :, 0].contiguous(), w3
 
 
 @pytest.mark.parametrize("C,K1,Cout3,groups,P", [(128, 128, 256, 1, 300), (256, 256, 128, 4, 200),

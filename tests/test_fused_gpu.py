@@ -11,6 +11,7 @@ import pytest
 import torch
 
 from tests import golden_util as GU
+from tests.chain_ref import f16x2_fields as _h2, f16x2_second as _h2_second    # shared with the chain edge suite
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-4
@@ -54,28 +55,6 @@ def _w3(w):
 
 
 PRECISIONS = [0, 1, 3]   # S4G_GEMM_FP32, S4G_GEMM_BF16X3, S4G_GEMM_F16X2
-
-
-def _h2(w, *tensors, floor=0.0):
-    """Descriptor fields of the f16x2 mode: scaled fp16 planes of W, per-channel
-    inverse scales, one 64-slot amax row per input tensor (the slot position is
-    arbitrary) and a zeroed out_amax row."""
-    from s4g_release_amd.fused import fragment_order, split_f16x2
-    k = w.shape[-1]
-    kp = (k + 15) // 16 * 16
-    w16 = w.new_zeros(w.shape[:-1] + (kp,))
-    w16[..., :k] = w
-    planes, inv = split_f16x2(w16)
-    kw = dict(W_f16x2=planes, w_inv_scale=inv, a_amax_floor=float(floor),
-              out_amax=torch.zeros(64, device=w.device))
-    if w.shape[-2] % 32 == 0:     # enables the chain kernel's single-layer form where the shape qualifies
-        p4 = planes if planes.dim() == 4 else planes.unsqueeze(1)
-        kw["W_f16x2_frag"] = fragment_order(p4)
-    for name, t in zip(("a_amax", "a_amax2"), [t for t in tensors if t is not None]):
-        row = torch.zeros(64, device=w.device)
-        row[17] = t.abs().max()
-        kw[name] = row
-    return kw
 
 
 def _check_out_amax(kw, out):
@@ -343,14 +322,6 @@ def test_model_with_and_without_pregathered_rows(dev, monkeypatch):
         assert err < TOL * max(1.0, a[k].abs().max().item()), (k, err)
 
 
-def _h2_second(W2):
-    """W2_f16x2_frag / w2_inv_scale of the layer fused behind (groups leading)."""
-    from s4g_release_amd.fused import fragment_order, split_f16x2
-    planes, inv = split_f16x2(W2.contiguous())
-    p4 = planes if planes.dim() == 4 else planes.unsqueeze(1)
-    return fragment_order(p4), inv
-
-
 @pytest.mark.parametrize("C,Cout2,epi,groups,P", [
     (128, 256, 1, 1, 37 * 64),     # SA0 shape: plain loader, max over 64 rows
     (128, 128, 1, 1, 3 * 64),      # odd number of centroids: half-empty last workgroup
@@ -542,7 +513,9 @@ def test_gemm_chain_supported_query_matches_dispatch(dev):
     assert lib.s4g_gemm_chain_supported(0, 0, 64, 64) == 0
     assert lib.s4g_gemm_chain_supported(0, 1, 256, 512) == 0      # deep first layer only with STORE
     assert lib.s4g_gemm_chain_supported(0, 0, 512, 1024) == 0
-    for loader, epi, C, k16, P in [(0, 0, 128, 128, 200), (0, 1, 512, 512, 128), (0, 0, 256, 512, 70)]:
+    assert lib.s4g_gemm_chain_supported(0, 0, 256, 1024) == 1     # ... four panels deep (tests/test_chain_edges_gpu.py, h)
+    for loader, epi, C, k16, P in [(0, 0, 128, 128, 200), (0, 1, 512, 512, 128), (0, 0, 256, 512, 70),
+                                   (0, 0, 256, 1024, 70)]:
         g = torch.Generator(device="cpu").manual_seed(C)
         A = torch.randn(P, k16, generator=g).to(dev)
         W1 = (torch.randn(C, k16, generator=g) / k16 ** 0.5).to(dev)
