@@ -63,7 +63,10 @@ extern "C" {
  *     and collision grading of grasp frames against a labelled scene cloud with normals); s4g_local_search_f32 /
  *     s4g_local_search_workspace_bytes (the data generator's per-frame local grasp search); s4g_darboux_frames_f32 /
  *     s4g_darboux_frames_workspace_bytes (the Darboux frames that search starts from); s4g_match_normals_f32 /
- *     s4g_match_normals_workspace_bytes (the scene normals a view's points take over in front of those frames). */
+ *     s4g_match_normals_workspace_bytes (the scene normals a view's points take over in front of those frames);
+ *     s4g_contact_search_f32 / s4g_contact_search_workspace_bytes (the contact model's grading of every scene frame),
+ *     s4g_match_nearest_f32 (the nearest scene point of every view point) and s4g_contact_select_f32 (the contact
+ *     model's per-view-point normal and best frame). */
 #define S4G_ABI_VERSION 14
 
 /* ---------------------------------------------------------------------------
@@ -848,6 +851,93 @@ int s4g_match_normals_f32(const float *query_b3n, const float *scene_b3m, const 
                           const float *camera_b3 /* may be NULL */, int64_t B, int64_t N, int64_t M, float radius,
                           int32_t max_nn, float *normals_b3n, int32_t *count_bn, int32_t *flags_bn,
                           void *workspace, size_t workspace_bytes, s4g_stream_t stream);
+
+/* The nearest scene point of every view point (csrc/match_normals.hip): the max_nn = 1 search of
+ * TorchPrecomputedSingleViewPointCloud._find_match (data_gen/pcd_classes/torch_contact_single_view_point_cloud.py:
+ * 142-150), returning the index.  The same grid, fp32 distance rule, strict radius, "(distance, then lower index)
+ * wins" and index-order fallback as s4g_match_normals_f32, whose build and query code it shares: the same bits from
+ * the grid and from the fallback.  nearest_bn int32 (B, N): the scene index, or -1 where no scene point is inside the
+ * radius or the query is not finite.  A scene point that is not finite is never a neighbour.
+ * radius in (0, 1e18), N and M < 2^30, M >= 1, B <= 65 535 (S4G_EINVAL otherwise).
+ * Workspace: what s4g_match_normals_workspace_bytes gives for (B, N, M); contents need not be initialised. */
+int s4g_match_nearest_f32(const float *query_b3n, const float *scene_b3m, int64_t B, int64_t N, int64_t M,
+                          float radius, int32_t *nearest_bn, void *workspace, size_t workspace_bytes,
+                          s4g_stream_t stream);
+
+/* Grading of the contact model's labels (csrc/contact_search.hip): TorchPrecomputedSingleViewPointCloud.finger_hand
+ * with _table_collision_check (data_gen/pcd_classes/torch_contact_single_view_point_cloud.py:236-294) for every scene
+ * frame of every scene, without host synchronisation.  The reference grades a frame from global_to_local and the
+ * scene alone and repeats that for every view point that picked the frame; here a scene frame is graded once.
+ * g2l (B, F, 4, 4) fp32 row-major, the scene's global_to_local; xyz (B, 3, M) fp32; labels (B, M) int32.
+ * frame_count_b (device, may be NULL): rows at or past frame_count_b[b] are not scanned and read invalid, label
+ * no_label and 0 everywhere else.
+ * nz, ny, nx in [1, 4]: the lengths of HEIGHT_SEARCH, WIDTH_SEARCH, LENGTH_SEARCH (S4G_EINVAL otherwise); P = nz * ny *
+ * nx placements, index (iz * ny + iy) * nx + ix: the reference's loops (:270-279), dz outer, dx inner.
+ * params10 (HOST pointer) = {FINGER_LENGTH, BOTTOM_LENGTH, HALF_HAND_THICKNESS, HALF_BOTTOM_WIDTH, HALF_BOTTOM_SPACE,
+ *   BACK_COLLISION_MARGIN, TABLE_HEIGHT + TABLE_COLLISION_OFFSET, max |dx|, max |dy|, max |dz|} (the last three size
+ *   the bounding cull only); no_label = the label of a frame without one (len(NAME_LIST)).
+ * tables_2z3y2x (DEVICE pointer, 2 nz + 3 ny + 2 nx floats) = {-HHT + dz [nz], HHT + dz [nz], -HBS + dy [ny],
+ *   HBS + dy [ny], dy [ny], -BOTTOM_LENGTH + dx [nx], FINGER_LENGTH + dx [nx]}: every bound formed in double and
+ *   rounded to fp32 once, as torch compares an fp32 tensor with a Python scalar.
+ * Per frame, local = g2l @ [p; 1] in fp32 as s4g_eval_frames_f32 forms it, once per scene point; per placement, with
+ * every inequality strict (:271-286):
+ *   z_bool = z < HHT + dz and z > -HHT + dz;  y_bool = y < HBS + dy and y > -HBS + dy;  abs_y = |y + dy| (one fp32
+ *   add; the sign of dy in y_bool and in abs_y is the reference's);  y_collision = abs_y > HBS and abs_y < HBW;
+ *   x_bool = x > -BOTTOM_LENGTH + dx and x < FINGER_LENGTH + dx;
+ *   finger = count(z & x & y_collision);  close = count(x & z & y_bool);  behind = count of close points with x <
+ *   BACK_COLLISION_MARGIN (the reference's min() < margin wherever the region is not empty);  multi_label = the
+ *   close region holds more than one label.  A point that is not finite is in no region.
+ * A frame is valid when no corner of the CENTRED gripper box (local_to_global @ GRIPPER_BOUND) is below params10[6]
+ * and every placement has finger == 0, close > 0, behind == 0 and one label.  The reference returns at the first
+ * failing placement; validity is the AND over the placements, so all are counted in one pass.
+ * Decisions.  (1) An empty close region makes the reference raise (min() of an empty tensor): here the frame is
+ *   invalid and fail bit 4 is set.  (2) local_to_global is the rigid inverse [R^T | -R^T t] formed in the kernel from
+ *   g2l, not torch.inverse; g2l must be rigid and is not checked.  (3) A g2l entry that is not finite: the frame is
+ *   not scanned, invalid, counts 0, fail = bit 5 alone.  (4) The table verdict covers the centred box only:
+ *   LOCAL_SEARCH_TO_LOCAL (:18-28) is written element by element into an expand()ed tensor, the writes alias and all
+ *   nine matrices end as the identity, so _table_collision_check never sees a shifted box.
+ * Outputs:
+ *   ints_bfp4  int32 (B, F, P, 4) = {finger, close, behind, multi_label}, counted whatever the table verdict
+ *   table_bf   int32 (B, F): 1 where the centred box collides with the table
+ *   valid_bf   int32 (B, F);  label_bf int32 (B, F): the close region's label of the LAST placement (dz = dy = dx = 0
+ *              as shipped, :293) where the frame is valid, else no_label
+ *   fail_bf    int32 (B, F), over all placements: bit 0 = table, bit 1 = finger, bit 2 = behind, bit 3 = several
+ *              labels, bit 4 = empty close region, bit 5 = a g2l entry that is not finite; valid = (fail == 0)
+ * Run-to-run bit-identical and batch invariant: counts and label extrema by integer atomics, no floating-point
+ * atomics.  M < 2^30, F < 2^30 (the frame loop runs inside the kernel), B <= 65 535.
+ * Cost: every scene point is transformed for every frame, M * F * 18 flops; a point inside the widened box's
+ * circumsphere then costs the region tests.  There is no spatial index over the scene.
+ * Workspace: s4g_contact_search_workspace_bytes(B, M, F, P) bytes (20 per placement), 256-byte aligned; contents
+ * need not be initialised; every launch of the call is a kernel. */
+size_t s4g_contact_search_workspace_bytes(int64_t B, int64_t M, int64_t F, int64_t P);
+int s4g_contact_search_f32(const float *g2l_bf44, const float *xyz_b3m, const int32_t *labels_bm, int64_t B, int64_t M,
+                           int64_t F, int64_t nz, int64_t ny, int64_t nx, const float *params10, int32_t no_label,
+                           const float *tables_2z3y2x, const int64_t *frame_count_b, int32_t *ints_bfp4,
+                           int32_t *table_bf, int32_t *valid_bf, int32_t *label_bf, int32_t *fail_bf, void *workspace,
+                           size_t workspace_bytes, s4g_stream_t stream);
+
+/* The contact model's label per view point (csrc/contact_search.hip): the rest of _find_match (:146-173) and of
+ * run_score (:189-208) of torch_contact_single_view_point_cloud.py, one thread per view point, without host
+ * synchronisation.  nearest (B, N) int32 from s4g_match_nearest_f32 (run on the noise-free reference cloud); cloud
+ * (B, 3, N) the noisy view; scene_normals (B, 3, M); camera (B, 3) the camera location; offsets (B, M + 1) and order
+ * (B, F) int32: a CSR whose row i lists the scene frames of scene point i in ascending frame index (the order of
+ * np.nonzero(frame_point_index == i), :152), any number of them; valid (B, F) int32 from s4g_contact_search_f32;
+ * search, antipodal (B, F) fp32 the scene's scores.  Per view point, i = nearest:
+ *   n = scene_normals[:, i], or (0, 0, 1) where i is -1 (:146-151); n / |n| in double, a zero normal giving NaN as
+ *     numpy does (:166); turned towards the camera by the rule of s4g_match_normals_f32 (ref = camera - cloud point,
+ *     not the reference-cloud point); rounded to fp32 once;
+ *   score of a frame = min(log(search) / 6.5, 1) * antipodal in fp32, a NaN kept as torch.min keeps it (:189-193);
+ *   the fold (:200-206): best = 0; for each valid frame of i in ascending frame index: best > s skips it, else best = s
+ *     and arg = frame -- an equal score picks the later frame, a NaN propagates as in the reference;
+ *   the point is valid when best > 0 (:208).
+ * Outputs: normals_b3n fp32 (B, 3, N); best_frame_bn int32 (B, N) the scene frame of a valid point, else -1;
+ * point_score_bn fp32 (B, N) = best; valid_index_bn int32 (B, N) the valid view points in ascending order, then -1;
+ * count_b int64 (B).  N, M, F < 2^30, M >= 1, B <= 65 535 (S4G_EINVAL otherwise).  No workspace. */
+int s4g_contact_select_f32(const int32_t *nearest_bn, const float *cloud_b3n, const float *scene_normals_b3m,
+                           const float *camera_b3, const int32_t *offsets_bm1, const int32_t *order_bf,
+                           const int32_t *valid_bf, const float *search_bf, const float *antipodal_bf, int64_t B,
+                           int64_t N, int64_t M, int64_t F, float *normals_b3n, int32_t *best_frame_bn,
+                           float *point_score_bn, int32_t *valid_index_bn, int64_t *count_b, s4g_stream_t stream);
 
 /* ---- next row f3: cloud pre-processing on device -------------------------
  * Single-scene passes in front of the network (reference

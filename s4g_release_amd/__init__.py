@@ -42,3 +42,17 @@ def label_view(*args, **kwargs):
     `grade_local_search` in one call.  See `postprocess.label_view`."""
     from .postprocess import label_view as _label
     return _label(*args, **kwargs)
+
+
+def grade_contact_frames(*args, **kwargs):
+    """The contact model's grading of every scene frame of every scene in one call.  See
+    `postprocess.grade_contact_frames`."""
+    from .postprocess import grade_contact_frames as _grade
+    return _grade(*args, **kwargs)
+
+
+def label_contact_view(*args, **kwargs):
+    """View cloud in, contact-model labels out: `match_nearest`, the frames of every scene point and the per-point
+    fold over the graded scene frames in one call.  See `postprocess.label_contact_view`."""
+    from .postprocess import label_contact_view as _label
+    return _label(*args, **kwargs)

@@ -1,7 +1,9 @@
 // Scene-normal transfer of the data generator's label pipeline for every view point of every scene:
 // TorchSingleViewPointCloud._find_normal (data_gen/pcd_classes/torch_single_view_point_cloud.py:135-150), which loops
 // over the view with one kd-tree search_hybrid_vector_3d(radius, max_nn) each, then normalises and orients the cloud.
-// Contract: include/s4g_ops.h (s4g_match_normals_f32).
+// Contract: include/s4g_ops.h (s4g_match_normals_f32).  s4g_match_nearest_f32 -- the max_nn = 1 search of
+// TorchPrecomputedSingleViewPointCloud._find_match (torch_contact_single_view_point_cloud.py:142-150), the index alone --
+// runs the same build and the same query loop and stops before the normals.
 //
 // Neighbourhood: a toroidal 64^3 cell grid over the SCENE (the keys; the queries are another set) with the cell edge
 // just above the radius and the cell coordinates of grid.h, built with the library's own stable radix sort instead of
@@ -185,10 +187,13 @@ __device__ __forceinline__ double mn_wave_sum(double v) {
   return v;
 }
 
+// NEAREST: the search alone with max_nn = 1 (s4g_match_nearest_f32): the kept key's index, or -1; no normal is read.
+template <bool NEAREST>
 __global__ __launch_bounds__(MN_THREADS) void match_query_kernel(
     const float* __restrict__ query, const float* __restrict__ scene, const float* __restrict__ scene_normals,
     const float* __restrict__ camera, int N, int M, float r2, float inv_h, int max_nn, MatchWs ws,
-    float* __restrict__ normals, int32_t* __restrict__ count, int32_t* __restrict__ flags) {
+    float* __restrict__ normals, int32_t* __restrict__ count, int32_t* __restrict__ flags,
+    int32_t* __restrict__ nearest) {
   __shared__ uint64_t lists[MN_WAVES][MN_LIST];
   const int b = blockIdx.y;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -196,7 +201,7 @@ __global__ __launch_bounds__(MN_THREADS) void match_query_kernel(
   if (q >= N) return;   // the whole wave
   const float* __restrict__ q0 = query + (size_t)b * 3 * N;
   const float* __restrict__ p0 = scene + (size_t)b * 3 * M;
-  const float* __restrict__ n0 = scene_normals + (size_t)b * 3 * M;
+  const float* __restrict__ n0 = NEAREST ? nullptr : scene_normals + (size_t)b * 3 * M;
   const float x = q0[q], y = q0[N + q], z = q0[2 * (size_t)N + q];
   const bool q_ok = mn_finite(x) && mn_finite(y) && mn_finite(z);
   MnSelect s;
@@ -256,6 +261,10 @@ __global__ __launch_bounds__(MN_THREADS) void match_query_kernel(
   }
   s.cut();   // ascending, at most max_nn
   const int k = s.n < max_nn ? s.n : max_nn;
+  if constexpr (NEAREST) {
+    if (lane == 0) nearest[(size_t)b * N + q] = k > 0 ? (int32_t)(uint32_t)s.list[0] : -1;
+    return;
+  }
   // the kept normals, rank r in lane r, summed in double by a fixed butterfly
   double ax = 0.0, ay = 0.0, az = 0.0;
   bool bad = false;
@@ -318,15 +327,14 @@ extern "C" size_t s4g_match_normals_workspace_bytes(int64_t B, int64_t N, int64_
   return s4g::match_ws(nullptr, s4g::mn_chunk(B, M), M, nullptr);
 }
 
-extern "C" int s4g_match_normals_f32(const float* query_b3n, const float* scene_b3m, const float* scene_normals_b3m,
-                                     const float* camera_b3, int64_t B, int64_t N, int64_t M, float radius,
-                                     int32_t max_nn, float* normals_b3n, int32_t* count_bn, int32_t* flags_bn,
-                                     void* workspace, size_t workspace_bytes, s4g_stream_t stream) {
-  using namespace s4g;
-  if (B < 0 || B > 65535 || N < 0 || N >= (1ll << 30) || M < 1 || M >= (1ll << 30)) return S4G_EINVAL;
-  if (!(radius > 0.f) || !(radius < 1e18f) || max_nn < 1 || max_nn > MN_MAX_NN) return S4G_EINVAL;
-  if (B == 0 || N == 0) return S4G_OK;
-  if (!query_b3n || !scene_b3m || !scene_normals_b3m || !normals_b3n || !count_bn || !flags_bn) return S4G_EINVAL;
+namespace s4g {
+
+// The build (clear, keys, sort, scan, order) and the query launch both entry points share; nearest_bn != NULL selects
+// the index-only query.
+static int match_run(const float* query_b3n, const float* scene_b3m, const float* scene_normals_b3m,
+                     const float* camera_b3, int64_t B, int64_t N, int64_t M, float radius, int32_t max_nn,
+                     float* normals_b3n, int32_t* count_bn, int32_t* flags_bn, int32_t* nearest_bn, void* workspace,
+                     size_t workspace_bytes, s4g_stream_t stream) {
   hipStream_t st = (hipStream_t)stream;
   const float r2 = radius * radius;   // fp32 product, as for the ball query
   // cell edge slightly above the radius, as for the ball query (grid.h)
@@ -355,12 +363,47 @@ extern "C" int s4g_match_normals_f32(const float* query_b3n, const float* scene_
     if (int rc = exclusive_scan_i32(w.scan, scan_ws_bytes(cells), w.count, w.start, cells, st)) return rc;
     hipLaunchKernelGGL(match_order_kernel, bgrid, dim3(MN_BUILD_THREADS), 0, st, sc, (int)M, w);
     S4G_LAUNCH_CHECK();
-    hipLaunchKernelGGL(match_query_kernel, dim3((unsigned)((N + MN_WAVES - 1) / MN_WAVES), (unsigned)Bc),
-                       dim3(MN_THREADS), 0, st, query_b3n + (size_t)b0 * 3 * N, sc,
-                       scene_normals_b3m + (size_t)b0 * 3 * M, camera_b3 ? camera_b3 + (size_t)b0 * 3 : nullptr, (int)N,
-                       (int)M, r2, inv_h, (int)max_nn, w, normals_b3n + (size_t)b0 * 3 * N, count_bn + (size_t)b0 * N,
-                       flags_bn + (size_t)b0 * N);
+    const dim3 qgrid((unsigned)((N + MN_WAVES - 1) / MN_WAVES), (unsigned)Bc);
+    if (nearest_bn) {
+      hipLaunchKernelGGL(match_query_kernel<true>, qgrid, dim3(MN_THREADS), 0, st, query_b3n + (size_t)b0 * 3 * N, sc,
+                         (const float*)nullptr, (const float*)nullptr, (int)N, (int)M, r2, inv_h, 1, w,
+                         (float*)nullptr, (int32_t*)nullptr, (int32_t*)nullptr, nearest_bn + (size_t)b0 * N);
+    } else {
+      hipLaunchKernelGGL(match_query_kernel<false>, qgrid, dim3(MN_THREADS), 0, st, query_b3n + (size_t)b0 * 3 * N, sc,
+                         scene_normals_b3m + (size_t)b0 * 3 * M, camera_b3 ? camera_b3 + (size_t)b0 * 3 : nullptr,
+                         (int)N, (int)M, r2, inv_h, (int)max_nn, w, normals_b3n + (size_t)b0 * 3 * N,
+                         count_bn + (size_t)b0 * N, flags_bn + (size_t)b0 * N, (int32_t*)nullptr);
+    }
     S4G_LAUNCH_CHECK();
   }
   return S4G_OK;
+}
+
+}  // namespace s4g
+
+extern "C" int s4g_match_normals_f32(const float* query_b3n, const float* scene_b3m, const float* scene_normals_b3m,
+                                     const float* camera_b3, int64_t B, int64_t N, int64_t M, float radius,
+                                     int32_t max_nn, float* normals_b3n, int32_t* count_bn, int32_t* flags_bn,
+                                     void* workspace, size_t workspace_bytes, s4g_stream_t stream) {
+  using namespace s4g;
+  if (B < 0 || B > 65535 || N < 0 || N >= (1ll << 30) || M < 1 || M >= (1ll << 30)) return S4G_EINVAL;
+  if (!(radius > 0.f) || !(radius < 1e18f) || max_nn < 1 || max_nn > MN_MAX_NN) return S4G_EINVAL;
+  if (B == 0 || N == 0) return S4G_OK;
+  if (!query_b3n || !scene_b3m || !scene_normals_b3m || !normals_b3n || !count_bn || !flags_bn) return S4G_EINVAL;
+  return match_run(query_b3n, scene_b3m, scene_normals_b3m, camera_b3, B, N, M, radius, max_nn, normals_b3n, count_bn,
+                   flags_bn, nullptr, workspace, workspace_bytes, stream);
+}
+
+// The max_nn = 1 search of TorchPrecomputedSingleViewPointCloud._find_match
+// (data_gen/pcd_classes/torch_contact_single_view_point_cloud.py:142-150): the index alone.
+extern "C" int s4g_match_nearest_f32(const float* query_b3n, const float* scene_b3m, int64_t B, int64_t N, int64_t M,
+                                     float radius, int32_t* nearest_bn, void* workspace, size_t workspace_bytes,
+                                     s4g_stream_t stream) {
+  using namespace s4g;
+  if (B < 0 || B > 65535 || N < 0 || N >= (1ll << 30) || M < 1 || M >= (1ll << 30)) return S4G_EINVAL;
+  if (!(radius > 0.f) || !(radius < 1e18f)) return S4G_EINVAL;
+  if (B == 0 || N == 0) return S4G_OK;
+  if (!query_b3n || !scene_b3m || !nearest_bn) return S4G_EINVAL;
+  return match_run(query_b3n, scene_b3m, nullptr, nullptr, B, N, M, radius, 1, nullptr, nullptr, nullptr, nearest_bn,
+                   workspace, workspace_bytes, stream);
 }

@@ -921,3 +921,366 @@ def label_view(cloud, normals, scene_points, scene_normals, scene_labels, config
         scene_points, scene_normals, scene_labels = scene_points[None], scene_normals[None], scene_labels[None]
     s = grade_local_search(d.points, d.frames, scene_points, scene_normals, scene_labels, cfg, d.frame_count)
     return ViewLabels(s, d, map_cloud_index(s.valid_index, d.frame_index), matched)
+
+
+CS_MAX_LIST = 4                            # the compiled maximum of each shift list (csrc/contact_search.hip)
+FAIL_TABLE, FAIL_FINGER, FAIL_BEHIND, FAIL_LABELS, FAIL_EMPTY, FAIL_NONFINITE = 1, 2, 4, 8, 16, 32
+
+
+@dataclass
+class ContactSearchConfig:
+    """The constants of the contact model's label search: the shift lists of
+    data_gen/pcd_classes/torch_contact_single_view_point_cloud.py:11-15, the gripper and table constants of
+    `LocalSearchConfig` (data_gen/configs/config.py:17,40,50-56,89) and the label of a frame without one
+    (`len(NAME_LIST)`, :125)."""
+    width_search: tuple = (-0.005, 0.005, 0)
+    height_search: tuple = (-0.005, 0.005, 0)
+    length_search: tuple = (0,)
+    table_height: float = 0.75
+    back_collision_margin: float = 0.0
+    half_bottom_width: float = 0.057
+    bottom_length: float = 0.08
+    finger_width: float = 0.023
+    half_hand_thickness: float = 0.012
+    finger_length: float = 0.09
+    table_collision_offset: float = 0.005
+    no_label: int = 122
+
+    @property
+    def half_bottom_space(self):
+        return self.half_bottom_width - self.finger_width
+
+    @property
+    def shape(self):
+        """(nz, ny, nx): heights, widths and lengths; placement (iz * ny + iy) * nx + ix, the reference's loop order."""
+        return len(self.height_search), len(self.width_search), len(self.length_search)
+
+    @property
+    def placements(self):
+        nz, ny, nx = self.shape
+        return nz * ny * nx
+
+    def check(self):
+        for name, n in zip(("height_search", "width_search", "length_search"), self.shape):
+            if not 1 <= n <= CS_MAX_LIST:
+                raise ValueError("%s needs 1..%d entries, got %d" % (name, CS_MAX_LIST, n))
+
+    def tables(self):
+        """The bounds the reference compares against, each formed in Python floats and rounded to fp32 ONCE (torch
+        compares an fp32 tensor with a Python scalar in fp32) -> dict of fp32 CPU tensors `zlo`, `zhi` (nz), `ylo`,
+        `yhi`, `dy` (ny), `xlo`, `xhi` (nx).  The sign of dy in `ylo` / `yhi` (+) and in |y + dy| is the reference's
+        (:274-276)."""
+        self.check()
+        hht, hbs = self.half_hand_thickness, self.half_bottom_space
+        f64 = lambda v: torch.tensor(v, dtype=torch.float64).to(torch.float32)      # noqa: E731  (one rounding)
+        return {"zlo": f64([-hht + float(d) for d in self.height_search]),
+                "zhi": f64([hht + float(d) for d in self.height_search]),
+                "ylo": f64([-hbs + float(d) for d in self.width_search]),
+                "yhi": f64([hbs + float(d) for d in self.width_search]),
+                "dy": f64([float(d) for d in self.width_search]),
+                "xlo": f64([-self.bottom_length + float(d) for d in self.length_search]),
+                "xhi": f64([self.finger_length + float(d) for d in self.length_search])}
+
+
+@dataclass
+class ContactSearch:
+    """What `grade_contact_frames` returns: device tensors, one row per scene frame.  `ints` (B, F, P, 4) = {finger,
+    close, behind, multi_label} per placement, `table_i32`, `valid_i32`, `objects_label`, `fail` (B, F) int32 are the
+    kernel's own outputs (include/s4g_ops.h has the layout and the bits of `fail`)."""
+    ints: torch.Tensor
+    table_i32: torch.Tensor
+    valid_i32: torch.Tensor
+    objects_label: torch.Tensor
+    fail: torch.Tensor
+    g2l: torch.Tensor
+    frame_count: torch.Tensor
+    config: ContactSearchConfig
+    unbatched: bool = False
+
+    finger = property(lambda self: self.ints[..., 0])
+    close = property(lambda self: self.ints[..., 1])
+    behind = property(lambda self: self.ints[..., 2])
+    multi_label = property(lambda self: self.ints[..., 3] != 0)
+    table_collision = property(lambda self: self.table_i32 != 0)
+    valid = property(lambda self: self.valid_i32 != 0)
+
+
+def grade_contact_frames(global_to_local, scene_points, scene_labels, config=None, frame_count=None):
+    """The contact model's frame grading -- `TorchPrecomputedSingleViewPointCloud.finger_hand` with
+    `_table_collision_check` (data_gen/pcd_classes/torch_contact_single_view_point_cloud.py:236-294), which `run_score`
+    (:183-185) loops over every (view point, frame) pair -- for every SCENE frame of every scene in one sync-free,
+    graph-capturable call -> `ContactSearch`.  Grading reads `global_to_local` and the scene alone, so a scene frame
+    is graded once, whichever view points of whichever views pick it.
+
+    global_to_local (B, F, 4, 4) fp32 rigid transforms (`TorchContactScenePointCloud.global_to_local`); scene_points
+    (B, 3, M) fp32; scene_labels (B, M) int32; one unbatched scene gets a leading 1.  frame_count (B,) on the device
+    (optional): rows at or past it are not scanned and read invalid.  Per frame P = |height| x |width| x |length|
+    placements (9 as shipped), counted in one pass; a frame is valid when the centred gripper box clears the table
+    and every placement has no finger point, a close region that is not empty, no close point behind the margin and
+    one label.  `objects_label` is the close region's label of the last placement, else `config.no_label`.
+
+    Four decisions.  (1) An empty close region makes the reference raise; here the frame is invalid (`fail` bit 4).
+    (2) `local_to_global` is the rigid inverse [R^T | -R^T t] formed in the kernel, not `torch.inverse`;
+    global_to_local must be rigid and is not checked.  (3) An entry that is not finite makes the frame invalid (`fail`
+    bit 5).  (4) The table verdict covers the centred box only: the reference's nine search matrices alias one
+    identity (:18-28)."""
+    cfg = config or ContactSearchConfig()
+    cfg.check()
+    for name, t in (("global_to_local", global_to_local), ("scene_points", scene_points),
+                    ("scene_labels", scene_labels)):
+        if not isinstance(t, torch.Tensor) or t.device.type != "cuda":
+            raise RuntimeError("%s must be a CUDA tensor (there is no CPU fallback)" % name)
+    unbatched = global_to_local.dim() == 3
+    if unbatched:
+        global_to_local, scene_points, scene_labels = global_to_local[None], scene_points[None], scene_labels[None]
+    xyz = _F._f32c(scene_points, "scene_points")
+    if scene_labels.dtype != torch.int32:
+        raise RuntimeError("scene_labels must be int32, got %s" % scene_labels.dtype)
+    if global_to_local.dtype != torch.float32:
+        raise RuntimeError("global_to_local must be float32")
+    if xyz.dim() != 3 or xyz.size(1) != 3 or xyz.size(2) < 1:
+        raise RuntimeError("scene_points must be (B, 3, M)")
+    B, _, M = xyz.shape
+    if tuple(scene_labels.shape) != (B, M):
+        raise RuntimeError("scene_labels must be (B, M)")
+    if global_to_local.dim() != 4 or global_to_local.size(0) != B or tuple(global_to_local.shape[2:]) != (4, 4):
+        raise RuntimeError("global_to_local must be (B, F, 4, 4)")
+    if len({xyz.device, scene_labels.device, global_to_local.device}) != 1:
+        raise RuntimeError("global_to_local, scene_points and scene_labels must live on one device")
+    dev = xyz.device
+    F = global_to_local.shape[1]
+    g2l, lab = global_to_local.contiguous(), scene_labels.contiguous()
+    cnt = None
+    if frame_count is not None:
+        if tuple(frame_count.shape) != (B,):
+            raise RuntimeError("frame_count must be (B,)")
+        cnt = frame_count.to(device=dev, dtype=torch.int64).contiguous()
+    nz, ny, nx = cfg.shape
+    P = cfg.placements
+    tb = cfg.tables()
+    tables = _small_on_device(torch.cat([tb[k] for k in ("zlo", "zhi", "ylo", "yhi", "dy", "xlo", "xhi")]),
+                              torch.float32, dev)
+    ints = torch.empty((B, F, P, 4), dtype=torch.int32, device=dev)
+    table, valid, label, fail = (torch.empty((B, F), dtype=torch.int32, device=dev) for _ in range(4))
+    params = (ctypes.c_float * 10)(cfg.finger_length, cfg.bottom_length, cfg.half_hand_thickness,
+                                   cfg.half_bottom_width, cfg.half_bottom_space, cfg.back_collision_margin,
+                                   cfg.table_height + cfg.table_collision_offset,
+                                   max(abs(float(v)) for v in cfg.length_search),
+                                   max(abs(float(v)) for v in cfg.width_search),
+                                   max(abs(float(v)) for v in cfg.height_search))
+    nbytes = _cabi.lib().s4g_contact_search_workspace_bytes(B, M, F, P)
+    ws = torch.empty((max(int(nbytes), 1),), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        rc = _cabi.lib().s4g_contact_search_f32(g2l.data_ptr(), xyz.data_ptr(), lab.data_ptr(), B, M, F, nz, ny, nx,
+                                                params, int(cfg.no_label), tables.data_ptr(),
+                                                None if cnt is None else cnt.data_ptr(), ints.data_ptr(),
+                                                table.data_ptr(), valid.data_ptr(), label.data_ptr(), fail.data_ptr(),
+                                                ws.data_ptr(), int(nbytes), _F._stream())
+    _cabi.check(rc, "contact_search")
+    return ContactSearch(ints, table, valid, label, fail, g2l, cnt, cfg, unbatched)
+
+
+def match_nearest(cloud, scene_points, radius=CURVATURE_RADIUS):
+    """The `max_nn = 1` search of `TorchPrecomputedSingleViewPointCloud._find_match` (:142-150) for every view point of
+    every scene: cloud (B, 3, N), scene_points (B, 3, M) fp32 -> (B, N) int32, the index of the nearest scene point by
+    `match_normals`' rule (fp32 squared distance < radius^2, strict; the lower index wins a tie), -1 where there is
+    none or the view point is not finite.  Unbatched inputs get a leading 1."""
+    for name, t in (("cloud", cloud), ("scene_points", scene_points)):
+        if not isinstance(t, torch.Tensor) or t.device.type != "cuda":
+            raise RuntimeError("%s must be a CUDA tensor (there is no CPU fallback)" % name)
+    if not float(radius) > 0.0:
+        raise ValueError("radius must be positive, got %r" % (radius,))
+    if cloud.dim() == 2:
+        cloud = cloud[None]
+        if scene_points.dim() == 2:
+            scene_points = scene_points[None]
+    xyz = _F._f32c(cloud, "cloud")
+    pts = _F._f32c(scene_points, "scene_points")
+    if xyz.dim() != 3 or xyz.size(1) != 3:
+        raise RuntimeError("cloud must be (B, 3, N)")
+    B, _, N = xyz.shape
+    if pts.dim() != 3 or pts.size(0) != B or pts.size(1) != 3 or pts.size(2) < 1:
+        raise RuntimeError("scene_points must be (B, 3, M) with M >= 1")
+    if xyz.device != pts.device:
+        raise RuntimeError("cloud and scene_points must live on one device")
+    M = pts.size(2)
+    nearest = torch.empty((B, N), dtype=torch.int32, device=xyz.device)
+    nbytes = _cabi.lib().s4g_match_normals_workspace_bytes(B, N, M)
+    ws = torch.empty((max(int(nbytes), 1),), dtype=torch.uint8, device=xyz.device)
+    with torch.cuda.device(xyz.device):
+        rc = _cabi.lib().s4g_match_nearest_f32(xyz.data_ptr(), pts.data_ptr(), B, N, M, float(radius),
+                                               nearest.data_ptr(), ws.data_ptr(), int(nbytes), _F._stream())
+    _cabi.check(rc, "match_nearest")
+    return nearest
+
+
+def frames_by_point(frame_point_index, num_points, frame_count=None):
+    """The scene frames of every scene point as a CSR, without a sync: frame_point_index (B, F) int -> (`offsets`
+    (B, num_points + 1) int32, `order` (B, F) int32); row i of scene b is order[b, offsets[b, i]:offsets[b, i + 1]],
+    the frames whose point is i in ascending frame index -- the order of `np.nonzero(frame_point_index == i)` (:152).
+    A stable sort by point; rows at or past frame_count[b] and indices outside [0, num_points) sort behind every point."""
+    B, F = frame_point_index.shape
+    dev = frame_point_index.device
+    key = frame_point_index.to(torch.int64)
+    dead = (key < 0) | (key >= num_points)
+    if frame_count is not None:
+        dead = dead | (torch.arange(F, device=dev).view(1, F) >= frame_count.view(B, 1))
+    key = torch.where(dead, key.new_full((), num_points), key)
+    skey, order = torch.sort(key, dim=1, stable=True)
+    points = torch.arange(num_points + 1, device=dev, dtype=torch.int64).view(1, -1).expand(B, -1).contiguous()
+    offsets = torch.searchsorted(skey.contiguous(), points)
+    return offsets.to(torch.int32).contiguous(), order.to(torch.int32).contiguous()
+
+
+@dataclass
+class ContactLabels:
+    """What `label_contact_view` returns: device tensors, one column per view point.  `nearest` (B, N) int32 the
+    matched scene point or -1, `normals` (B, 3, N) fp32, `best_frame` (B, N) int32 the scene frame of a valid point or
+    -1, `point_score` (B, N) fp32, `valid_index` (B, N) int32 the valid view points in ascending order then -1,
+    `count` (B,) int64; `search`: the `ContactSearch` of the scene frames; `cloud` the noisy view as given."""
+    nearest: torch.Tensor
+    normals: torch.Tensor
+    best_frame: torch.Tensor
+    point_score: torch.Tensor
+    valid_index: torch.Tensor
+    count: torch.Tensor
+    search: ContactSearch
+    cloud: torch.Tensor
+    scene_search_score: torch.Tensor
+    scene_antipodal_score: torch.Tensor
+    unbatched: bool = False
+
+    valid = property(lambda self: self.best_frame >= 0)
+
+    def _of_best(self, per_frame, fill):
+        if per_frame.shape[1] == 0:
+            return per_frame.new_full(self.best_frame.shape, fill)
+        got = torch.gather(per_frame, 1, self.best_frame.clamp(min=0).to(torch.int64))
+        return torch.where(self.best_frame >= 0, got, got.new_full((), fill))
+
+    search_score = property(lambda self: self._of_best(self.scene_search_score, 0.0))
+    antipodal_score = property(lambda self: self._of_best(self.scene_antipodal_score, 0.0))
+    objects_label = property(lambda self: self._of_best(self.search.objects_label, self.search.config.no_label))
+
+    def frames_of(self, frame=None):
+        """`local_to_global` of the scene frames `frame` (B, K) (default: `best_frame`): (B, K, 4, 4) fp32, the rigid
+        inverse [R^T | -R^T t] of `global_to_local` (`se3_inverse`; not `torch.inverse`, :120).  Rows whose frame is -1
+        are 0."""
+        frame = self.best_frame if frame is None else frame
+        g2l = self.search.g2l
+        B, K = frame.shape
+        if g2l.shape[1] == 0:
+            return torch.zeros((B, K, 4, 4), dtype=torch.float32, device=g2l.device)
+        idx = frame.to(device=g2l.device, dtype=torch.int64)
+        g = torch.gather(g2l, 1, idx.clamp(min=0).view(B, K, 1, 1).expand(B, K, 4, 4))
+        return torch.where((idx >= 0).view(B, K, 1, 1), se3_inverse(g), torch.zeros((), device=g2l.device))
+
+    def dump(self, b=0):
+        """The dictionary of the reference's `dump()` (:217-226) for scene b, in the WORLD frame (the camera transform
+        is the caller's, as for `LocalSearch.dump`).  Reads the count on the host."""
+        n = int(self.count[b])
+        vi = self.valid_index[b, :n].long()
+        bf = self.best_frame[b:b + 1, vi]
+        return {"search_score": self.search_score[b, vi].cpu().numpy(),
+                "antipodal_score": self.antipodal_score[b, vi].cpu().numpy(),
+                "valid_frame": self.frames_of(bf)[0].cpu().numpy(),
+                "valid_index": vi.cpu().numpy(),
+                "point_cloud": self.cloud[b].cpu().numpy(),
+                "objects_label": self.objects_label[b, vi].cpu().numpy()}
+
+
+def label_contact_view(reference_cloud, cloud, scene_points, scene_normals, camera, frame_point_index, search_score,
+                       antipodal_score, search=None, global_to_local=None, scene_labels=None, config=None,
+                       frame_count=None, radius=CURVATURE_RADIUS):
+    """`TorchPrecomputedSingleViewPointCloud.run_score` (data_gen/pcd_classes/torch_contact_single_view_point_cloud.py:
+    129-226): view cloud in, contact-model labels out, in one sync-free, graph-capturable call -> `ContactLabels`.
+
+    reference_cloud (B, 3, N) the noise-free view points the match runs on (`reference_cloud[index_in_ref]`); cloud
+    (B, 3, N) the noisy view, used for the orientation and returned; scene_points, scene_normals (B, 3, M); camera
+    (B, 3) or (3,) the camera location; frame_point_index (B, F) int32 the scene point of each scene frame, in any
+    order; search_score, antipodal_score (B, F) fp32 the scene's scores.  search: the `ContactSearch` of the scene's
+    frames (`grade_contact_frames`; grade once per scene, select once per view), or None: it is computed from
+    global_to_local (B, F, 4, 4), scene_labels (B, M), config and frame_count.  One unbatched view gets a leading 1.
+
+    Per view point: i = the nearest scene point (`match_nearest` on reference_cloud); the normal of i, or (0, 0, 1)
+    without one, normalised in double, turned towards the camera seen from the NOISY point, rounded once; the score
+    min(log(search) / 6.5, 1) * antipodal of every valid frame of i, folded as the reference folds (:200-206: best
+    starts at 0, a frame replaces it unless best > score, so an equal score picks the later frame); valid where the
+    best score is positive.  Every frame of a scene point takes part: the reference's ten-frames-per-point buffer is
+    not reproduced."""
+    for name, t in (("reference_cloud", reference_cloud), ("cloud", cloud), ("scene_points", scene_points),
+                    ("scene_normals", scene_normals), ("camera", camera), ("frame_point_index", frame_point_index),
+                    ("search_score", search_score), ("antipodal_score", antipodal_score)):
+        if not isinstance(t, torch.Tensor) or t.device.type != "cuda":
+            raise RuntimeError("%s must be a CUDA tensor (there is no CPU fallback)" % name)
+    unbatched = cloud.dim() == 2
+    if unbatched:
+        reference_cloud, cloud = reference_cloud[None], cloud[None]
+        if scene_points.dim() == 2:
+            scene_points, scene_normals = scene_points[None], scene_normals[None]
+            scene_labels = None if scene_labels is None else scene_labels[None]
+        if frame_point_index.dim() == 1:
+            frame_point_index, search_score, antipodal_score = (frame_point_index[None], search_score[None],
+                                                                antipodal_score[None])
+            global_to_local = None if global_to_local is None else global_to_local[None]
+    ref = _F._f32c(reference_cloud, "reference_cloud")
+    xyz = _F._f32c(cloud, "cloud")
+    pts = _F._f32c(scene_points, "scene_points")
+    nrm = _F._f32c(scene_normals, "scene_normals")
+    ss = _F._f32c(search_score, "search_score")
+    aps = _F._f32c(antipodal_score, "antipodal_score")
+    if xyz.dim() != 3 or xyz.size(1) != 3:
+        raise RuntimeError("cloud must be (B, 3, N)")
+    B, _, N = xyz.shape
+    if tuple(ref.shape) != (B, 3, N):
+        raise RuntimeError("reference_cloud must be (B, 3, N) like cloud")
+    if pts.dim() != 3 or pts.size(0) != B or pts.size(1) != 3 or pts.size(2) < 1:
+        raise RuntimeError("scene_points must be (B, 3, M) with M >= 1")
+    M = pts.size(2)
+    if tuple(nrm.shape) != (B, 3, M):
+        raise RuntimeError("scene_normals must be (B, 3, M) like scene_points")
+    if frame_point_index.dtype != torch.int32:
+        raise RuntimeError("frame_point_index must be int32, got %s" % frame_point_index.dtype)
+    if frame_point_index.dim() != 2 or frame_point_index.size(0) != B:
+        raise RuntimeError("frame_point_index must be (B, F)")
+    F = frame_point_index.size(1)
+    if tuple(ss.shape) != (B, F) or tuple(aps.shape) != (B, F):
+        raise RuntimeError("search_score and antipodal_score must be (B, F) like frame_point_index")
+    cam = _F._f32c(camera, "camera")
+    if cam.dim() == 1 and cam.numel() == 3:
+        cam = cam.view(1, 3).expand(B, 3)
+    if tuple(cam.shape) != (B, 3):
+        raise RuntimeError("camera must be (B, 3) or (3,)")
+    cam = cam.contiguous()
+    if len({ref.device, xyz.device, pts.device, nrm.device, cam.device, frame_point_index.device, ss.device,
+            aps.device}) != 1:
+        raise RuntimeError("every input must live on one device")
+    dev = xyz.device
+    if search is None:
+        if global_to_local is None or scene_labels is None:
+            raise RuntimeError("without search=, global_to_local and scene_labels are needed to grade the frames")
+        search = grade_contact_frames(global_to_local, pts, scene_labels, config, frame_count)
+    elif frame_count is None:
+        frame_count = search.frame_count
+    if tuple(search.valid_i32.shape) != (B, F) or search.valid_i32.device != dev:
+        raise RuntimeError("search must hold the (B, F) frames of frame_point_index, on the same device")
+    cnt = None
+    if frame_count is not None:
+        if tuple(frame_count.shape) != (B,):
+            raise RuntimeError("frame_count must be (B,)")
+        cnt = frame_count.to(device=dev, dtype=torch.int64)
+    nearest = match_nearest(ref, pts, radius)
+    offsets, order = frames_by_point(frame_point_index, M, cnt)
+    normals = torch.empty((B, 3, N), dtype=torch.float32, device=dev)
+    best = torch.empty((B, N), dtype=torch.int32, device=dev)
+    score = torch.empty((B, N), dtype=torch.float32, device=dev)
+    valid_index = torch.empty((B, N), dtype=torch.int32, device=dev)
+    count = torch.empty((B,), dtype=torch.int64, device=dev)
+    with torch.cuda.device(dev):
+        rc = _cabi.lib().s4g_contact_select_f32(nearest.data_ptr(), xyz.data_ptr(), nrm.data_ptr(), cam.data_ptr(),
+                                                offsets.data_ptr(), order.data_ptr(), search.valid_i32.data_ptr(),
+                                                ss.data_ptr(), aps.data_ptr(), B, N, M, F, normals.data_ptr(),
+                                                best.data_ptr(), score.data_ptr(), valid_index.data_ptr(),
+                                                count.data_ptr(), _F._stream())
+    _cabi.check(rc, "contact_select")
+    return ContactLabels(nearest, normals, best, score, valid_index, count, search, xyz, ss, aps, unbatched)
