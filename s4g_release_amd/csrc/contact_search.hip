@@ -13,7 +13,7 @@
 // coordinates) than the circumradius of the box widened by the largest shifts is in no region of any placement.
 //
 //   cs_setup_kernel   the neutral values of every accumulator (no memset: every launch of the call is a kernel)
-//   cs_scan_kernel    points outer / frames inner like ls_scan_kernel: per placement the counts in the fingers / in
+//   cs_scan_kernel    a cloud sweep (frame_sweep.h: points outer, frames inner): per placement the counts in the fingers / in
 //                     the close region / of close points behind the margin and the label minimum / maximum, in LDS,
 //                     then the workspace; integer atomics only, so the result does not depend on their order
 //   cs_finish_kernel  per frame: the table verdict of the centred box, the verdicts of the placements, the failure
@@ -30,9 +30,7 @@
 // the valid frames of that scene point in ascending frame index (:200-206).
 //
 // Limits: M < 2^30, F < 2^30 (the frame loops run inside the kernels or over grid.x), B <= 65 535 (grid.y / grid.z).
-#include <limits.h>
-
-#include "s4g_common.h"
+#include "frame_sweep.h"
 
 namespace s4g {
 
@@ -58,29 +56,13 @@ struct CsTables {
       xhi[CS_MAX_LIST];
 };
 
-static inline int cs_chunks(int64_t M) {
-  int64_t c = (M + CS_CHUNK_POINTS - 1) / CS_CHUNK_POINTS;
-  if (c < CS_MIN_CHUNKS) c = CS_MIN_CHUNKS;
-  if (c > CS_MAX_CHUNKS) c = CS_MAX_CHUNKS;
-  return (int)c;
-}
-
-__device__ __forceinline__ bool cs_finite(float v) { return fabsf(v) <= 3.402823466e38f; }
-__device__ __forceinline__ bool cs_finite(double v) { return fabs(v) <= 1.7976931348623157e308; }
-
-__device__ __forceinline__ int cs_rows(const int64_t* __restrict__ frame_count, int b, int F) {
-  if (!frame_count) return F;
-  return (int)min((int64_t)F, max((int64_t)0, frame_count[b]));      // padding rows: never scanned
-}
-
 // one thread per accumulator set
 __global__ __launch_bounds__(256) void cs_setup_kernel(int* __restrict__ acc, size_t sets) {
   const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
   if (i >= sets) return;
   int* a = acc + i * CS_ACC;
-  a[0] = a[1] = a[2] = 0;
-  a[3] = INT_MAX;
-  a[4] = INT_MIN;
+#pragma unroll
+  for (int w = 0; w < CS_ACC; ++w) a[w] = acc_neutral(w);
 }
 
 __global__ __launch_bounds__(256) void cs_scan_kernel(
@@ -91,49 +73,39 @@ __global__ __launch_bounds__(256) void cs_scan_kernel(
   __shared__ int live[CS_SLOTS];
   __shared__ int cnt[CS_SLOTS][CS_MAX_P][CS_ACC];
   __shared__ CsTables tb;
-  const int b = blockIdx.z, chunk = blockIdx.y, t = threadIdx.x;
+  const int b = blockIdx.z, t = threadIdx.x;
   const int nz = p.nz, ny = p.ny, nx = p.nx, P = nz * ny * nx;
   const float* px = xyz + (size_t)b * 3 * M;
   const int* lab = labels + (size_t)b * M;
-  const int nc = (M + (int)gridDim.y - 1) / (int)gridDim.y;
-  const int i_lo = chunk * nc, i_hi = min(M, i_lo + nc);
-  if (i_lo >= i_hi) return;                          // an empty chunk (workgroup-uniform, before any barrier)
+  const ChunkRange rg = chunk_range(M);
+  if (rg.empty()) return;
   if (t < nz) { tb.zlo[t] = tables[t]; tb.zhi[t] = tables[nz + t]; }
   if (t < ny) { tb.ylo[t] = tables[2 * nz + t]; tb.yhi[t] = tables[2 * nz + ny + t]; tb.dy[t] = tables[2 * nz + 2 * ny + t]; }
   if (t < nx) { tb.xlo[t] = tables[2 * nz + 3 * ny + t]; tb.xhi[t] = tables[2 * nz + 3 * ny + nx + t]; }
-  const int fmax = cs_rows(frame_count, b, F);
+  const int fmax = frame_rows(frame_count, b, F);
   for (int j0 = 0; (int)blockIdx.x + CS_GX * j0 < fmax; j0 += CS_SLOTS) {
     __syncthreads();                                  // (the previous pass's accumulators have been flushed)
-    const int left = (fmax - 1 - (int)blockIdx.x) / CS_GX + 1 - j0;       // frames of this workgroup from j0 on
-    const int nslot = left < CS_SLOTS ? left : CS_SLOTS;
+    const int nslot = pass_slots(fmax, CS_GX, j0, CS_SLOTS);
     if (t < nslot) {
       const float* G = g2l + ((size_t)b * F + blockIdx.x + (size_t)CS_GX * (j0 + t)) * 16;
       bool ok = true;
 #pragma unroll
       for (int c = 0; c < 16; ++c) {
         const float v = G[c];
-        ok = ok && cs_finite(v);
+        ok = ok && finite(v);
         if (c < 12) gl[t][c] = v;
       }
       live[t] = ok ? 1 : 0;                           // a frame with an entry that is not finite is never scanned
     }
     for (int i = t; i < nslot * P * CS_ACC; i += 256) {
-      const int w = i % CS_ACC;
-      ((int*)cnt[i / (P * CS_ACC)])[i % (P * CS_ACC)] = w == 3 ? INT_MAX : w == 4 ? INT_MIN : 0;
+      ((int*)cnt[i / (P * CS_ACC)])[i % (P * CS_ACC)] = acc_neutral(i % CS_ACC);
     }
     __syncthreads();
-    for (int i0 = i_lo + t; i0 < i_hi; i0 += 256 * CS_U) {
-      float x[CS_U], y[CS_U], z[CS_U];
-      bool in[CS_U];
-#pragma unroll
-      for (int u = 0; u < CS_U; ++u) {
-        const int i = i0 + 256 * u;
-        in[u] = i < i_hi;
-        const int j = in[u] ? i : i0;                 // (i0 < i_hi: always a point of the chunk)
-        x[u] = px[j];
-        y[u] = px[(size_t)M + j];
-        z[u] = px[2 * (size_t)M + j];
-      }
+    // (the narrow bound, not sweep_end, and masked lanes on point i0 < hi: no ballot or shuffle below, and this kernel
+    //  has no scalar register to spare at 8 waves per SIMD: frame_sweep.h)
+    for (int i0 = rg.lo + t; i0 < rg.hi; i0 += 256 * CS_U) {
+      PointBlock<CS_U> pt;
+      pt.load(px, M, i0, rg.hi, i0);
       for (int sl = 0; sl < nslot; ++sl) {
         if (!live[sl]) continue;                      // workgroup-uniform
         float g[12];
@@ -141,11 +113,10 @@ __global__ __launch_bounds__(256) void cs_scan_kernel(
         for (int c = 0; c < 12; ++c) g[c] = gl[sl][c];
 #pragma unroll
         for (int u = 0; u < CS_U; ++u) {
-          const float lx = g[0] * x[u] + g[1] * y[u] + g[2] * z[u] + g[3];
-          const float ly = g[4] * x[u] + g[5] * y[u] + g[6] * z[u] + g[7];
-          const float lz = g[8] * x[u] + g[9] * y[u] + g[10] * z[u] + g[11];
+          const LocalPoint l = local_point(g, pt.x[u], pt.y[u], pt.z[u]);
+          const float lx = l.x, ly = l.y, lz = l.z;
           // the cull; a point that is not finite gives NaN or inf here and is in no region
-          if (!in[u] || !(lx * lx + ly * ly + lz * lz < p.r2cull)) continue;
+          if (!pt.in[u] || !(lx * lx + ly * ly + lz * lz < p.r2cull)) continue;
           unsigned zb = 0, xb = 0, yb = 0, yc = 0;
           for (int k = 0; k < nz; ++k) zb |= (((lz < tb.zhi[k]) && (lz > tb.zlo[k])) ? 1u : 0u) << k;       // :271-272
           if (!zb) continue;
@@ -158,7 +129,7 @@ __global__ __launch_bounds__(256) void cs_scan_kernel(
           }
           if (!(yb | yc)) continue;
           const bool behind = lx < p.margin;                                                                // :286
-          const int lb = lab[i0 + 256 * u];
+          const int lb = lab[i0 + 256 * u];       // (= pt.idx[u] of a point in range; four registers less)
           for (int kz = 0; kz < nz; ++kz) {
             if (!((zb >> kz) & 1u)) continue;
             for (int ky = 0; ky < ny; ++ky) {
@@ -204,17 +175,17 @@ __global__ __launch_bounds__(256) void cs_finish_kernel(
   if (f >= (size_t)F) return;
   const size_t row = (size_t)b * F + f;
   const int P = p.nz * p.ny * p.nx;
-  const bool row_in = f < (size_t)cs_rows(frame_count, b, F);
+  const bool row_in = f < (size_t)frame_rows(frame_count, b, F);
   float G[16];
-  bool finite = true;
+  bool all_finite = true;
 #pragma unroll
   for (int c = 0; c < 16; ++c) {
     G[c] = g2l[row * 16 + c];
-    finite = finite && cs_finite(G[c]);
+    all_finite = all_finite && finite(G[c]);
   }
   int* oi = ints + row * P * 4;
   int bits = 0, hit = 0, lbl = p.no_label;
-  if (!row_in || !finite) {
+  if (!row_in || !all_finite) {
     for (int i = 0; i < P * 4; ++i) oi[i] = 0;
     if (row_in) bits = 32;
   } else {
@@ -238,7 +209,7 @@ __global__ __launch_bounds__(256) void cs_finish_kernel(
     if (bits == 0) lbl = acc[(row * P + P - 1) * CS_ACC + 3];                       // :293, the last placement's label
   }
   table[row] = hit;
-  valid[row] = (row_in && finite && bits == 0) ? 1 : 0;
+  valid[row] = (row_in && all_finite && bits == 0) ? 1 : 0;
   label[row] = lbl;
   fail[row] = bits;
 }
@@ -265,7 +236,7 @@ __global__ __launch_bounds__(256) void cs_select_kernel(
   const float* cam = camera + (size_t)b * 3;
   const double rx = (double)cam[0] - (double)c0[q], ry = (double)cam[1] - (double)c0[(size_t)N + q],
                rz = (double)cam[2] - (double)c0[2 * (size_t)N + q];
-  if (cs_finite(rx) && cs_finite(ry) && cs_finite(rz)) {   // no reference direction otherwise: n stays
+  if (finite(rx) && finite(ry) && finite(rz)) {   // no reference direction otherwise: n stays
     if (nx == 0.0 && ny == 0.0 && nz == 0.0) {
       const double rl = sqrt(rx * rx + ry * ry + rz * rz);
       if (rl > 0.0) {
@@ -301,34 +272,12 @@ __global__ __launch_bounds__(256) void cs_select_kernel(
   best_frame[(size_t)b * N + q] = (best > 0.f) ? arg : -1;                         // :208
 }
 
-// one workgroup per scene: the valid view points in ascending order
-__global__ __launch_bounds__(256) void cs_compact_kernel(const int* __restrict__ best_frame, int N,
-                                                         int* __restrict__ valid_index, int64_t* __restrict__ count) {
-  __shared__ int wtot[4];
-  const int b = blockIdx.x, t = threadIdx.x, lane = t & 63, wave = t >> 6;
-  int base = 0;
-  for (int f0 = 0; f0 < N; f0 += 256) {
-    const int f = f0 + t;
-    const bool v = f < N && best_frame[(size_t)b * N + f] >= 0;
-    const uint64_t m = __ballot(v);
-    if (lane == 0) wtot[wave] = __popcll(m);
-    __syncthreads();
-    int off = base;
-    for (int w = 0; w < wave; ++w) off += wtot[w];
-    if (v) valid_index[(size_t)b * N + off + mask_rank(m)] = f;
-    base += wtot[0] + wtot[1] + wtot[2] + wtot[3];
-    __syncthreads();
-  }
-  for (int f = base + t; f < N; f += 256) valid_index[(size_t)b * N + f] = -1;
-  if (t == 0) count[b] = base;
-}
-
 }  // namespace s4g
 
 extern "C" size_t s4g_contact_search_workspace_bytes(int64_t B, int64_t M, int64_t F, int64_t P) {
   (void)M;
   if (B <= 0 || F <= 0 || P <= 0 || P > s4g::CS_MAX_P) return 0;
-  return (((size_t)B * (size_t)F * (size_t)P * s4g::CS_ACC * sizeof(int)) + 255) & ~(size_t)255;
+  return s4g::align256((size_t)B * (size_t)F * (size_t)P * s4g::CS_ACC * sizeof(int));
 }
 
 extern "C" int s4g_contact_search_f32(const float* g2l_bf44, const float* xyz_b3m, const int32_t* labels_bm, int64_t B,
@@ -360,7 +309,7 @@ extern "C" int s4g_contact_search_f32(const float* g2l_bf44, const float* xyz_b3
   int* acc = (int*)workspace;
   hipLaunchKernelGGL(cs_setup_kernel, dim3((unsigned)((sets + 255) / 256)), dim3(256), 0, st, acc, sets);
   S4G_LAUNCH_CHECK();
-  const dim3 grid(CS_GX, (unsigned)cs_chunks(M), (unsigned)B);
+  const dim3 grid(CS_GX, (unsigned)sweep_chunks(M, CS_CHUNK_POINTS, CS_MIN_CHUNKS, CS_MAX_CHUNKS), (unsigned)B);
   hipLaunchKernelGGL(cs_scan_kernel, grid, dim3(256), 0, st, xyz_b3m, (const int*)labels_bm, g2l_bf44, tables_2z3y2x,
                      (int)M, (int)F, p, acc, frame_count_b);
   S4G_LAUNCH_CHECK();
@@ -393,7 +342,7 @@ extern "C" int s4g_contact_select_f32(const int32_t* nearest_bn, const float* cl
                        normals_b3n, (int*)best_frame_bn, point_score_bn);
     S4G_LAUNCH_CHECK();
   }
-  hipLaunchKernelGGL(cs_compact_kernel, dim3((unsigned)B), dim3(256), 0, st, (const int*)best_frame_bn, (int)N,
+  hipLaunchKernelGGL(compact_valid_kernel<KeepNonNegative>, dim3((unsigned)B), dim3(256), 0, st, (const int*)best_frame_bn, (int)N,
                      (int*)valid_index_bn, count_b);
   S4G_LAUNCH_CHECK();
   return S4G_OK;

@@ -157,8 +157,6 @@ __device__ __forceinline__ void darboux_neighbours(bool grid, const DarbouxWs& w
   }
 }
 
-__device__ __forceinline__ bool db_finite(float v) { return fabsf(v) <= 3.402823466e38f; }
-
 __global__ __launch_bounds__(DB_THREADS) void darboux_frames_kernel(
     const float* __restrict__ xyz, const float* __restrict__ normals, const int32_t* __restrict__ frame_index,
     const int64_t* __restrict__ frame_count, int N, int F, float r2, float inv_h, int min_neighbours, int have_grid,
@@ -181,8 +179,8 @@ __global__ __launch_bounds__(DB_THREADS) void darboux_frames_kernel(
     px = p0[i]; py = p0[N + i]; pz = p0[2 * (size_t)N + i];
     const float nxf = n0[i], nyf = n0[N + i], nzf = n0[2 * (size_t)N + i];
     // a point or normal that is not finite still counts its neighbours (none, for a point that is not finite)
-    const bool own_bad = !(db_finite(px) && db_finite(py) && db_finite(pz) && db_finite(nxf) && db_finite(nyf) &&
-                           db_finite(nzf));
+    const bool own_bad = !(finite(px) && finite(py) && finite(pz) && finite(nxf) && finite(nyf) &&
+                           finite(nzf));
     const float ox = p0[0], oy = p0[N], oz = p0[2 * (size_t)N];
     const bool grid = have_grid && ws.grid.flags[b] == 0 && grid_coord_ok(px, ox, inv_h) &&
                       grid_coord_ok(py, oy, inv_h) && grid_coord_ok(pz, oz, inv_h);

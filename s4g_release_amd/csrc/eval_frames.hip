@@ -4,7 +4,7 @@
 // with no host synchronisation.
 //
 //   eval_init_kernel     the per-pose accumulators (workspace) to their neutral values
-//   eval_scan_kernel     first scan of the cloud: the counts behind the palm / in the fingers (s4g_common.h `gripper_regions`,
+//   eval_scan_kernel     first scan of the cloud: the counts behind the palm / in the fingers (frame_sweep.h `gripper_regions`,
 //                        which collision_counts_kernel calls too: the two integers are equal bit for bit), the
 //                        close-region count, its label minimum / maximum (more than one distinct label <=> min != max:
 //                        no `unique`) and its y extrema (ordered-integer atomics: order independent)
@@ -16,16 +16,16 @@
 //                        (pose, chunk) in the workspace
 //   eval_finish_kernel   flags, pairwise sum of the chunk partials in chunk order, means and score; padding rows read 0
 //
+// Both scans are cloud sweeps: frame_sweep.h has the skeleton and the full-wave bound their ballots rely on.
+//
 // The rejected alternative (compact the close region's (y, |n.y|) pairs into the workspace during the first scan and
 // reduce those): profiles/r09_eval_frames.md.
-#include <limits.h>
-
-#include "s4g_common.h"
+#include "frame_sweep.h"
 
 namespace s4g {
 
 struct EvalParams {
-  GripperBox box;                  // the collision counter's six values (s4g_common.h)
+  GripperBox box;                  // the collision counter's six values
   float back_threshold, finger_threshold, min_points, neighbor_depth;
 };
 
@@ -37,23 +37,6 @@ constexpr int EV_MAX_CHUNKS = 64;
 constexpr int EV_CHUNK_POINTS = 8192;
 constexpr int EV_ACC = 8;          // per-pose accumulator ints: back, finger, close, label min, label max, y max, y min, -
 
-static inline int eval_chunks(int64_t N) {
-  int64_t c = (N + EV_CHUNK_POINTS - 1) / EV_CHUNK_POINTS;
-  if (c < EV_MIN_CHUNKS) c = EV_MIN_CHUNKS;
-  if (c > EV_MAX_CHUNKS) c = EV_MAX_CHUNKS;
-  return (int)c;
-}
-
-static inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
-
-// a monotone map float -> int (and back: it is an involution) for every non-NaN value: atomicMax / atomicMin on it give
-// the float maximum / minimum whatever the order of arrival
-__device__ __forceinline__ int f2ord(float f) {
-  const int i = __float_as_int(f);
-  return i ^ ((i >> 31) & 0x7fffffff);
-}
-__device__ __forceinline__ float ord2f(int o) { return __int_as_float(o ^ ((o >> 31) & 0x7fffffff)); }
-
 // the verdicts of :83-111 from a pose's accumulators; scored = the pose reaches _antipodal_score
 __device__ __forceinline__ bool eval_gate(const int* __restrict__ a, const EvalParams& p, bool* collision, bool* multi) {
   *collision = ((double)a[0] > (double)p.back_threshold) || ((double)a[1] > (double)p.finger_threshold);   // :83,93
@@ -61,58 +44,38 @@ __device__ __forceinline__ bool eval_gate(const int* __restrict__ a, const EvalP
   return a[2] > 0 && !((double)a[2] < (double)p.min_points) && !*collision && !*multi;                    // :107-111
 }
 
-__device__ __forceinline__ int pose_rows(const int64_t* __restrict__ pose_count, int b, int K) {
-  if (!pose_count) return K;
-  return (int)min((int64_t)K, max((int64_t)0, pose_count[b]));     // padding rows: never scanned
-}
-
 __global__ __launch_bounds__(256) void eval_init_kernel(int* __restrict__ acc, int64_t n_pose) {
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (i >= n_pose * EV_ACC) return;
-  const int w = (int)(i % EV_ACC);
-  acc[i] = (w == 3 || w == 6) ? INT_MAX : (w == 4 || w == 5) ? INT_MIN : 0;
+  acc[i] = acc_neutral((int)(i % EV_ACC));
 }
 
-// Points outer, poses inner, like collision_counts_kernel: a workgroup keeps 1 024 points in registers and runs all its
-// poses over them.  Labels are read only where a wave has a close-region point (rare: the region is a few cm wide).
+// The cloud sweep of frame_sweep.h, points outer, poses inner: a workgroup keeps 1 024 points in registers and runs all
+// its poses over them.  Labels are read only where a wave has a close-region point (rare: the region is a few cm wide).
 __global__ __launch_bounds__(256) void eval_scan_kernel(
     const float* __restrict__ xyz, const int* __restrict__ labels, const float* __restrict__ g2l, int N, int K,
     EvalParams p, int* __restrict__ acc, const int64_t* __restrict__ pose_count, int invert_se3) {
   __shared__ float gl[EV_SLOTS][12];
   __shared__ int cnt[EV_SLOTS][EV_ACC];
-  const int b = blockIdx.z, chunk = blockIdx.y, t = threadIdx.x, lane = t & 63;
+  const int b = blockIdx.z, t = threadIdx.x, lane = t & 63;
   const float* px = xyz + (size_t)b * 3 * N;
   const int* lab = labels + (size_t)b * N;
-  const int nc = (N + (int)gridDim.y - 1) / (int)gridDim.y;
-  const int i_lo = chunk * nc, i_hi = min(N, i_lo + nc);
-  if (i_lo >= i_hi) return;                          // an empty chunk (workgroup-uniform, before any barrier)
-  const int kmax = pose_rows(pose_count, b, K);
+  const ChunkRange rg = chunk_range(N);
+  if (rg.empty()) return;
+  const int kmax = frame_rows(pose_count, b, K);
   for (int j0 = 0; blockIdx.x + EV_GX * j0 < kmax; j0 += EV_SLOTS) {
     __syncthreads();                                  // (the previous pass's tables have been read)
     if (t < EV_SLOTS) {
       const int k = blockIdx.x + EV_GX * (j0 + t);
-      cnt[t][0] = cnt[t][1] = cnt[t][2] = 0;
-      cnt[t][3] = INT_MAX; cnt[t][4] = INT_MIN; cnt[t][5] = INT_MIN; cnt[t][6] = INT_MAX;
+#pragma unroll
+      for (int w = 0; w < ACC_WORDS; ++w) cnt[t][w] = acc_neutral(w);
       if (k < kmax) load_g2l(g2l + ((size_t)b * K + k) * 16, invert_se3, gl[t]);
     }
     __syncthreads();
-    const int left = (kmax - 1 - (int)blockIdx.x) / EV_GX + 1 - j0;       // poses of this workgroup from j0 on
-    const int nslot = left < EV_SLOTS ? left : EV_SLOTS;
-    // (the bound is i_hi + 768, not i_hi: lanes of one wave differ by less than 64 in i0, so a wave that still holds an
-    //  in-range point is fully active -- the ballots and the 64-lane butterfly below rely on it)
-    for (int i0 = i_lo + t; i0 < i_hi + 256 * (EV_U - 1); i0 += 256 * EV_U) {
-      float x[EV_U], y[EV_U], z[EV_U];
-      bool in[EV_U];
-      int idx[EV_U];
-#pragma unroll
-      for (int u = 0; u < EV_U; ++u) {
-        const int i = i0 + 256 * u;
-        in[u] = i < i_hi;
-        idx[u] = in[u] ? i : i_hi - 1;               // masked lanes load the chunk's last point (always < N)
-        x[u] = px[idx[u]];
-        y[u] = px[(size_t)N + idx[u]];
-        z[u] = px[2 * (size_t)N + idx[u]];
-      }
+    const int nslot = pass_slots(kmax, EV_GX, j0, EV_SLOTS);
+    for (int i0 = rg.lo + t; i0 < sweep_end<EV_U>(rg.hi); i0 += 256 * EV_U) {
+      PointBlock<EV_U> pt;
+      pt.load(px, N, i0, rg.hi);
       for (int sl = 0; sl < nslot; ++sl) {
         float g[12];
 #pragma unroll
@@ -122,13 +85,13 @@ __global__ __launch_bounds__(256) void eval_scan_kernel(
         bool hit = false;
 #pragma unroll
         for (int u = 0; u < EV_U; ++u) {
-          const GripperRegions r = gripper_regions(g, x[u], y[u], z[u], p.box);
-          const bool cr = in[u] && r.closer;
-          nback += __popcll(__ballot(in[u] && r.back));      // wave-uniform
-          nfing += __popcll(__ballot(in[u] && r.fing));
+          const GripperRegions r = gripper_regions(g, pt.x[u], pt.y[u], pt.z[u], p.box);
+          const bool cr = pt.in[u] && r.closer;
+          nback += __popcll(__ballot(pt.in[u] && r.back));      // wave-uniform
+          nfing += __popcll(__ballot(pt.in[u] && r.fing));
           nclose += __popcll(__ballot(cr));
           if (cr) {
-            const int l = lab[idx[u]], o = f2ord(r.ly);
+            const int l = lab[pt.idx[u]], o = f2ord(r.ly);
             lmin = min(lmin, l); lmax = max(lmax, l);
             ymx = max(ymx, o); ymn = min(ymn, o);
             hit = true;
@@ -177,10 +140,9 @@ __global__ __launch_bounds__(256) void eval_band_kernel(
   const float* px = xyz + (size_t)b * 3 * N;
   const float* pn = normals + (size_t)b * 3 * N;
   const int nchunk = (int)gridDim.y;
-  const int nc = (N + nchunk - 1) / nchunk;
-  const int i_lo = chunk * nc, i_hi = min(N, i_lo + nc);
-  if (i_lo >= i_hi) return;                          // an empty chunk: eval_finish_kernel does not read its partials
-  const int kmax = pose_rows(pose_count, b, K);
+  const ChunkRange rg = chunk_range(N);
+  if (rg.empty()) return;                            // eval_finish_kernel does not read an empty chunk's partials
+  const int kmax = frame_rows(pose_count, b, K);
   for (int j0 = 0; blockIdx.x + EV_GX * j0 < kmax; j0 += EV_SLOTS) {
     __syncthreads();
     if (t < EV_SLOTS) {                               // (the first 32 lanes of wave 0)
@@ -210,21 +172,9 @@ __global__ __launch_bounds__(256) void eval_band_kernel(
     __syncthreads();
     const int nslot = nlive;
     if (nslot == 0) continue;                         // workgroup-uniform
-    // (the bound is i_hi + 768, not i_hi: lanes of one wave differ by less than 64 in i0, so a wave that still holds an
-    //  in-range point is fully active -- the ballots and the 64-lane butterfly below rely on it)
-    for (int i0 = i_lo + t; i0 < i_hi + 256 * (EV_U - 1); i0 += 256 * EV_U) {
-      float x[EV_U], y[EV_U], z[EV_U];
-      bool in[EV_U];
-      int idx[EV_U];
-#pragma unroll
-      for (int u = 0; u < EV_U; ++u) {
-        const int i = i0 + 256 * u;
-        in[u] = i < i_hi;
-        idx[u] = in[u] ? i : i_hi - 1;
-        x[u] = px[idx[u]];
-        y[u] = px[(size_t)N + idx[u]];
-        z[u] = px[2 * (size_t)N + idx[u]];
-      }
+    for (int i0 = rg.lo + t; i0 < sweep_end<EV_U>(rg.hi); i0 += 256 * EV_U) {
+      PointBlock<EV_U> pt;
+      pt.load(px, N, i0, rg.hi);
       for (int sl = 0; sl < nslot; ++sl) {
         float g[12];
 #pragma unroll
@@ -234,14 +184,14 @@ __global__ __launch_bounds__(256) void eval_band_kernel(
         float sl_ = 0.f, sr_ = 0.f;                   // this lane's (at most 4, nearly always at most 1) band terms
 #pragma unroll
         for (int u = 0; u < EV_U; ++u) {
-          const GripperRegions r = gripper_regions(g, x[u], y[u], z[u], p.box);
-          const bool cr = in[u] && r.closer;
+          const GripperRegions r = gripper_regions(g, pt.x[u], pt.y[u], pt.z[u], p.box);
+          const bool cr = pt.in[u] && r.closer;
           const bool il = cr && (r.ly > lthr), ir = cr && (r.ly < rthr);                     // :56-57
           nl += __popcll(__ballot(il));
           nr += __popcll(__ballot(ir));
           if (il || ir) {
             // n_local.y = row 1 of the rotation times the normal (:69), not re-normalised; |.| (:58-59)
-            const float a = fabsf(g[4] * pn[idx[u]] + g[5] * pn[(size_t)N + idx[u]] + g[6] * pn[2 * (size_t)N + idx[u]]);
+            const float a = fabsf(g[4] * pn[pt.idx[u]] + g[5] * pn[(size_t)N + pt.idx[u]] + g[6] * pn[2 * (size_t)N + pt.idx[u]]);
             if (il) sl_ += a;
             if (ir) sr_ += a;
           }
@@ -281,7 +231,7 @@ __global__ __launch_bounds__(64) void eval_finish_kernel(
   float* of = floats + ((size_t)b * K + k) * 5;
   int vi[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   float vf[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
-  if (k < pose_rows(pose_count, b, K)) {
+  if (k < frame_rows(pose_count, b, K)) {
     const int* a = acc + ((size_t)b * K + k) * EV_ACC;
     bool collision, multi;
     const bool scored = eval_gate(a, p, &collision, &multi);
@@ -325,8 +275,10 @@ __global__ __launch_bounds__(64) void eval_finish_kernel(
 
 extern "C" size_t s4g_eval_frames_workspace_bytes(int64_t B, int64_t N, int64_t K) {
   if (B <= 0 || N <= 0 || K <= 0) return 0;
+  using namespace s4g;
   const size_t poses = (size_t)B * (size_t)K;
-  return s4g::align256(poses * s4g::EV_ACC * sizeof(int)) + poses * (size_t)s4g::eval_chunks(N) * 4 * sizeof(float);
+  const size_t nchunk = (size_t)sweep_chunks(N, EV_CHUNK_POINTS, EV_MIN_CHUNKS, EV_MAX_CHUNKS);
+  return align256(poses * EV_ACC * sizeof(int)) + poses * nchunk * 4 * sizeof(float);
 }
 
 extern "C" int s4g_eval_frames_f32(const float* xyz_b3n, const float* normals_b3n, const int32_t* labels_bn,
@@ -342,7 +294,7 @@ extern "C" int s4g_eval_frames_f32(const float* xyz_b3n, const float* normals_b3
   EvalParams p = {{params10[0], params10[1], params10[2], params10[3], params10[4], params10[5]},
                   params10[6], params10[7], params10[8], params10[9]};
   hipStream_t st = (hipStream_t)stream;
-  const int nchunk = eval_chunks(N);
+  const int nchunk = sweep_chunks(N, EV_CHUNK_POINTS, EV_MIN_CHUNKS, EV_MAX_CHUNKS);
   const int64_t poses = B * K;
   int* acc = (int*)workspace;
   float* part = (float*)((char*)workspace + align256((size_t)poses * EV_ACC * sizeof(int)));

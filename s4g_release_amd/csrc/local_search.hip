@@ -11,20 +11,18 @@
 //
 //   ls_setup_kernel    per frame: the two gates (:257,259), [R^T | -R^T p] (:91-94), the L*T table verdicts (:224-241)
 //                      and the neutral values of the frame's accumulators (no memset: every launch of the call is a kernel)
-//   ls_scan_kernel     first scan, points outer / frames inner like eval_scan_kernel: the slab counters (:270-273) and,
+//   ls_scan_kernel     first scan, a cloud sweep (frame_sweep.h: points outer, frames inner): the slab counters (:270-273) and,
 //                      for the points that pass the cull, per placement that the table verdict lets through the counts
 //                      behind the palm / in the fingers /
 //                      in the close region, the label minimum / maximum and the ordered-integer y extrema; in LDS, then
 //                      the workspace
 //   ls_band_kernel     second scan, only for placements that reached the score: sum |n.y| over the two bands (:167-176)
 //                      in 2^-30 fixed point with INTEGER atomics -- order independent, so results are bit-identical from
-//                      run to run and batch invariant without a fixed reduction tree (eval_band_kernel keeps one partial
-//                      per (pose, chunk); 48 placements per frame would make that workspace 48 times as large)
+//                      run to run and batch invariant without a fixed reduction tree (one partial per (frame, chunk), as
+//                      the pose grading keeps, would make the workspace 48 times as large: 48 placements per frame)
 //   ls_finish_kernel   the gates in the reference's order, search score, label, antipodal score, frame validity (:348)
-//   ls_compact_kernel  valid_index: the valid frames of a scene in ascending order, -1 padded, and their count
-#include <limits.h>
-
-#include "s4g_common.h"
+//   compact_valid_kernel (frame_sweep.h)  valid_index: the valid frames of a scene in ascending order, -1 padded, and their count
+#include "frame_sweep.h"
 
 namespace s4g {
 
@@ -53,27 +51,6 @@ struct LsParams {
 struct LsTables {
   float dl[LS_MAX_L], lo[LS_MAX_L], hi[LS_MAX_L], cs[LS_MAX_T], sn[LS_MAX_T];
 };
-
-static inline int ls_chunks(int64_t N) {
-  int64_t c = (N + LS_CHUNK_POINTS - 1) / LS_CHUNK_POINTS;
-  if (c < LS_MIN_CHUNKS) c = LS_MIN_CHUNKS;
-  if (c > LS_MAX_CHUNKS) c = LS_MAX_CHUNKS;
-  return (int)c;
-}
-
-static inline size_t ls_align256(size_t v) { return (v + 255) & ~(size_t)255; }
-
-// monotone float <-> int map (an involution), as in eval_frames.hip: integer atomicMax / atomicMin give float extrema
-__device__ __forceinline__ int ls_f2ord(float f) {
-  const int i = __float_as_int(f);
-  return i ^ ((i >> 31) & 0x7fffffff);
-}
-__device__ __forceinline__ float ls_ord2f(int o) { return __int_as_float(o ^ ((o >> 31) & 0x7fffffff)); }
-
-__device__ __forceinline__ int ls_rows(const int64_t* __restrict__ frame_count, int b, int F) {
-  if (!frame_count) return F;
-  return (int)min((int64_t)F, max((int64_t)0, frame_count[b]));      // padding rows: never scanned
-}
 
 __device__ __forceinline__ void ls_load_tables(const float* __restrict__ tables, int L, int T, LsTables* s, int t) {
   if (t < L) { s->dl[t] = tables[t]; s->lo[t] = tables[L + t]; s->hi[t] = tables[2 * L + t]; }
@@ -106,7 +83,7 @@ __global__ __launch_bounds__(64) void ls_setup_kernel(
 #pragma unroll
   for (int i = 0; i < 9; ++i) r[i] = frames[row * 9 + i];
   const float px = points[row * 3], py = points[row * 3 + 1], pz = points[row * 3 + 2];
-  bool ok = f < ls_rows(frame_count, b, F);
+  bool ok = f < frame_rows(frame_count, b, F);
   float s = 0.f;
 #pragma unroll
   for (int i = 0; i < 9; ++i) s = s + fabsf(r[i]);
@@ -136,28 +113,14 @@ __global__ __launch_bounds__(64) void ls_setup_kernel(
       hit = hit || (m0 * cx + m1 * cy + m2 * cz + m3 < p.table_limit);               // :240
     }
     int* a = acc + (row * P + pl) * LS_ACC;
-    a[0] = a[1] = a[2] = 0;
-    a[3] = INT_MAX; a[4] = INT_MIN; a[5] = INT_MIN; a[6] = INT_MAX;
+#pragma unroll
+    for (int w = 0; w < ACC_WORDS; ++w) a[w] = acc_neutral(w);
     a[7] = (ok && hit) ? 1 : 0;
     bsum[(row * P + pl) * 2] = bsum[(row * P + pl) * 2 + 1] = 0ull;
     bcnt[(row * P + pl) * 2] = bcnt[(row * P + pl) * 2 + 1] = 0;
   }
   if (lane < p.L) slab[row * p.L + lane] = 0;
 }
-
-// the points of a sweep: LS_U per lane; masked lanes hold the chunk's last point (always < N)
-#define LS_LOAD_POINTS()                                      \
-  float x[LS_U], y[LS_U], z[LS_U];                            \
-  bool in[LS_U];                                              \
-  int idx[LS_U];                                              \
-  _Pragma("unroll") for (int u = 0; u < LS_U; ++u) {          \
-    const int i = i0 + 256 * u;                               \
-    in[u] = i < i_hi;                                         \
-    idx[u] = in[u] ? i : i_hi - 1;                            \
-    x[u] = px[idx[u]];                                        \
-    y[u] = px[(size_t)N + idx[u]];                            \
-    z[u] = px[2 * (size_t)N + idx[u]];                        \
-  }
 
 __global__ __launch_bounds__(256) void ls_scan_kernel(
     const float* __restrict__ xyz, const int* __restrict__ labels, const float* __restrict__ hdr,
@@ -169,19 +132,17 @@ __global__ __launch_bounds__(256) void ls_scan_kernel(
   __shared__ unsigned opn[LS_SLOTS][LS_MAX_L];      // per depth, the rolls whose table verdict lets the placement through
   __shared__ int cnt[LS_SLOTS][LS_MAX_P][LS_ACC];
   __shared__ LsTables tb;
-  const int b = blockIdx.z, chunk = blockIdx.y, t = threadIdx.x, lane = t & 63;
+  const int b = blockIdx.z, t = threadIdx.x, lane = t & 63;
   const int L = p.L, T = p.T, P = L * T;
   const float* px = xyz + (size_t)b * 3 * N;
   const int* lab = labels + (size_t)b * N;
-  const int nc = (N + (int)gridDim.y - 1) / (int)gridDim.y;
-  const int i_lo = chunk * nc, i_hi = min(N, i_lo + nc);
-  if (i_lo >= i_hi) return;                          // an empty chunk (workgroup-uniform, before any barrier)
+  const ChunkRange rg = chunk_range(N);
+  if (rg.empty()) return;
   ls_load_tables(tables, L, T, &tb, t);
-  const int fmax = ls_rows(frame_count, b, F);
+  const int fmax = frame_rows(frame_count, b, F);
   for (int j0 = 0; blockIdx.x + LS_GX * j0 < fmax; j0 += LS_SLOTS) {
     __syncthreads();                                  // (the previous pass's accumulators have been flushed)
-    const int left = (fmax - 1 - (int)blockIdx.x) / LS_GX + 1 - j0;       // frames of this workgroup from j0 on
-    const int nslot = left < LS_SLOTS ? left : LS_SLOTS;
+    const int nslot = pass_slots(fmax, LS_GX, j0, LS_SLOTS);
     if (t < nslot) {
       const float* h = hdr + ((size_t)b * F + blockIdx.x + LS_GX * (j0 + t)) * LS_HDR;
 #pragma unroll
@@ -197,14 +158,12 @@ __global__ __launch_bounds__(256) void ls_scan_kernel(
       opn[sl][d] = mask;
     }
     for (int i = t; i < nslot * P * LS_ACC; i += 256) {
-      const int w = i & (LS_ACC - 1);
-      ((int*)cnt[i / (P * LS_ACC)])[i % (P * LS_ACC)] = (w == 3 || w == 6) ? INT_MAX : (w == 4 || w == 5) ? INT_MIN : 0;
+      ((int*)cnt[i / (P * LS_ACC)])[i % (P * LS_ACC)] = acc_neutral(i & (LS_ACC - 1));
     }
     __syncthreads();
-    // (the bound is i_hi + 768, not i_hi: lanes of one wave differ by less than 64 in i0, so a wave that still holds an
-    //  in-range point is fully active -- the ballots below rely on it)
-    for (int i0 = i_lo + t; i0 < i_hi + 256 * (LS_U - 1); i0 += 256 * LS_U) {
-      LS_LOAD_POINTS()
+    for (int i0 = rg.lo + t; i0 < sweep_end<LS_U>(rg.hi); i0 += 256 * LS_U) {
+      PointBlock<LS_U> pt;
+      pt.load(px, N, i0, rg.hi);
       for (int sl = 0; sl < nslot; ++sl) {
         if (!live[sl]) continue;                      // a frame that failed a gate: never scanned (workgroup-uniform)
         float g[12];
@@ -214,9 +173,8 @@ __global__ __launch_bounds__(256) void ls_scan_kernel(
         unsigned m[LS_U];
 #pragma unroll
         for (int u = 0; u < LS_U; ++u) {
-          lx[u] = g[0] * x[u] + g[1] * y[u] + g[2] * z[u] + g[3];
-          ly[u] = g[4] * x[u] + g[5] * y[u] + g[6] * z[u] + g[7];
-          lz[u] = g[8] * x[u] + g[9] * y[u] + g[10] * z[u] + g[11];
+          const LocalPoint l = local_point(g, pt.x[u], pt.y[u], pt.z[u]);
+          lx[u] = l.x; ly[u] = l.y; lz[u] = l.z;
           m[u] = 0;
         }
         for (int d = 0; d < L; ++d) {                 // the depth slabs (:270-271): wave-uniform counts
@@ -224,7 +182,7 @@ __global__ __launch_bounds__(256) void ls_scan_kernel(
           int n = 0;
 #pragma unroll
           for (int u = 0; u < LS_U; ++u) {
-            const bool s = in[u] && (lx[u] < hi) && (lx[u] > lo);
+            const bool s = pt.in[u] && (lx[u] < hi) && (lx[u] > lo);
             n += __popcll(__ballot(s));
             m[u] |= (s ? 1u : 0u) << d;
           }
@@ -237,7 +195,7 @@ __global__ __launch_bounds__(256) void ls_scan_kernel(
           unsigned rolls = 0;
           for (int d = 0; d < L; ++d) rolls |= ((m[u] >> d) & 1u) ? opn[sl][d] : 0u;
           if (!rolls) continue;
-          const int lb = lab[idx[u]];
+          const int lb = lab[pt.idx[u]];
           for (int r = 0; r < T; ++r) {
             if (!((rolls >> r) & 1u)) continue;
             float yy, zz;
@@ -246,7 +204,7 @@ __global__ __launch_bounds__(256) void ls_scan_kernel(
             if (!((yy < p.hbw) && (yy > -p.hbw))) continue;                            // outside back, fingers and close region
             const bool closer = (yy < p.hbs) && (yy > -p.hbs);                         // :317-319
             const bool fing = (yy > p.hbs) || (yy < -p.hbs);                           // :306-312
-            const int o = ls_f2ord(yy);
+            const int o = f2ord(yy);
             for (int d = 0; d < L; ++d) {
               if (!((m[u] >> d) & 1u) || !((opn[sl][d] >> r) & 1u)) continue;
               int* a = cnt[sl][d * T + r];
@@ -297,19 +255,17 @@ __global__ __launch_bounds__(256) void ls_band_kernel(
   __shared__ unsigned long long bs[LS_SLOTS][LS_MAX_P][2];
   __shared__ int bc[LS_SLOTS][LS_MAX_P][2];
   __shared__ LsTables tb;
-  const int b = blockIdx.z, chunk = blockIdx.y, t = threadIdx.x;
+  const int b = blockIdx.z, t = threadIdx.x;
   const int L = p.L, T = p.T, P = L * T;
   const float* px = xyz + (size_t)b * 3 * N;
   const float* pn = normals + (size_t)b * 3 * N;
-  const int nc = (N + (int)gridDim.y - 1) / (int)gridDim.y;
-  const int i_lo = chunk * nc, i_hi = min(N, i_lo + nc);
-  if (i_lo >= i_hi) return;
+  const ChunkRange rg = chunk_range(N);
+  if (rg.empty()) return;
   ls_load_tables(tables, L, T, &tb, t);
-  const int fmax = ls_rows(frame_count, b, F);
+  const int fmax = frame_rows(frame_count, b, F);
   for (int j0 = 0; blockIdx.x + LS_GX * j0 < fmax; j0 += LS_SLOTS) {
     __syncthreads();
-    const int left = (fmax - 1 - (int)blockIdx.x) / LS_GX + 1 - j0;
-    const int nslot = left < LS_SLOTS ? left : LS_SLOTS;
+    const int nslot = pass_slots(fmax, LS_GX, j0, LS_SLOTS);
     if (t < nslot) {
       const float* h = hdr + ((size_t)b * F + blockIdx.x + LS_GX * (j0 + t)) * LS_HDR;
 #pragma unroll
@@ -325,7 +281,7 @@ __global__ __launch_bounds__(256) void ls_band_kernel(
       const int* a = acc + (row * P + pl) * LS_ACC;
       float lthr = __int_as_float(0x7f800000), rthr = __int_as_float(0xff800000);     // +inf, -inf: an empty band
       if (((const int*)(hdr + row * LS_HDR))[12] && ls_gate(a, slab[row * L + pl / T], p)) {
-        const float left_y = ls_ord2f(a[5]), right_y = ls_ord2f(a[6]);                          // :167-168
+        const float left_y = ord2f(a[5]), right_y = ord2f(a[6]);                          // :167-168
         const float depth = fminf(__fdiv_rn(__fsub_rn(left_y, right_y), 3.0f), p.nd);           // :169
         lthr = __fsub_rn(left_y, depth);                                                        // :171
         rthr = __fadd_rn(right_y, depth);                                                       // :172
@@ -339,8 +295,9 @@ __global__ __launch_bounds__(256) void ls_band_kernel(
     }
     __syncthreads();
     if (!anylive) continue;                           // workgroup-uniform: no cloud read for this pass
-    for (int i0 = i_lo + t; i0 < i_hi + 256 * (LS_U - 1); i0 += 256 * LS_U) {
-      LS_LOAD_POINTS()
+    for (int i0 = rg.lo + t; i0 < sweep_end<LS_U>(rg.hi); i0 += 256 * LS_U) {
+      PointBlock<LS_U> pt;
+      pt.load(px, N, i0, rg.hi);
       for (int sl = 0; sl < nslot; ++sl) {
         if (!live[sl]) continue;
         float g[12];
@@ -348,10 +305,9 @@ __global__ __launch_bounds__(256) void ls_band_kernel(
         for (int c = 0; c < 12; ++c) g[c] = gl[sl][c];
 #pragma unroll
         for (int u = 0; u < LS_U; ++u) {
-          if (!in[u]) continue;
-          const float lx = g[0] * x[u] + g[1] * y[u] + g[2] * z[u] + g[3];
-          const float ly = g[4] * x[u] + g[5] * y[u] + g[6] * z[u] + g[7];
-          const float lz = g[8] * x[u] + g[9] * y[u] + g[10] * z[u] + g[11];
+          if (!pt.in[u]) continue;
+          const LocalPoint l = local_point(g, pt.x[u], pt.y[u], pt.z[u]);
+          const float lx = l.x, ly = l.y, lz = l.z;
           unsigned m = 0;
           for (int d = 0; d < L; ++d) m |= (((lx < tb.hi[d]) && (lx > tb.lo[d])) ? 1u : 0u) << d;
           if (!m || !(ly * ly + lz * lz < p.r2lim)) continue;
@@ -359,7 +315,7 @@ __global__ __launch_bounds__(256) void ls_band_kernel(
           for (int d = 0; d < L; ++d) rolls |= ((m >> d) & 1u) ? lmask[sl][d] : 0u;
           if (!rolls) continue;                       // no placement of this point's slabs reached the score
           // the normal in the frame: rows 1 and 2 of R^T (:267); the roll below gives its y in the placement (:339-341)
-          const float nx = pn[idx[u]], ny = pn[(size_t)N + idx[u]], nz = pn[2 * (size_t)N + idx[u]];
+          const float nx = pn[pt.idx[u]], ny = pn[(size_t)N + pt.idx[u]], nz = pn[2 * (size_t)N + pt.idx[u]];
           const float ny_l = g[4] * nx + g[5] * ny + g[6] * nz;
           const float nz_l = g[8] * nx + g[9] * ny + g[10] * nz;
           for (int r = 0; r < T; ++r) {
@@ -413,7 +369,7 @@ __global__ __launch_bounds__(LS_MAX_P) void ls_finish_kernel(
         vi[0] = a[2];                                                 // :332-333
         vi[1] = a[3];                                                 // :334-336
         const size_t o = (row * P + pl) * 2;
-        // torch.mean (:176): an empty band gives NaN there, in eval_frames and here
+        // torch.mean (:176): an empty band gives NaN there, in the pose grading and here
         const float ml = (float)((double)bsum[o] * (1.0 / (double)LS_FIX) / (double)bcnt[o]);
         const float mr = (float)((double)bsum[o + 1] * (1.0 / (double)LS_FIX) / (double)bcnt[o + 1]);
         score = __fmul_rn(ml, mr);
@@ -430,28 +386,6 @@ __global__ __launch_bounds__(LS_MAX_P) void ls_finish_kernel(
   if (pl == 0) valid[row] = any ? 1 : 0;
 }
 
-// one workgroup per scene: the valid frames in ascending order
-__global__ __launch_bounds__(256) void ls_compact_kernel(const int* __restrict__ valid, int F,
-                                                         int* __restrict__ valid_index, int64_t* __restrict__ count) {
-  __shared__ int wtot[4];
-  const int b = blockIdx.x, t = threadIdx.x, lane = t & 63, wave = t >> 6;
-  int base = 0;
-  for (int f0 = 0; f0 < F; f0 += 256) {
-    const int f = f0 + t;
-    const bool v = f < F && valid[(size_t)b * F + f] != 0;
-    const uint64_t m = __ballot(v);
-    if (lane == 0) wtot[wave] = __popcll(m);
-    __syncthreads();
-    int off = base;
-    for (int w = 0; w < wave; ++w) off += wtot[w];
-    if (v) valid_index[(size_t)b * F + off + mask_rank(m)] = f;
-    base += wtot[0] + wtot[1] + wtot[2] + wtot[3];
-    __syncthreads();
-  }
-  for (int f = base + t; f < F; f += 256) valid_index[(size_t)b * F + f] = -1;
-  if (t == 0) count[b] = base;
-}
-
 struct LsLayout {
   size_t hdr, acc, slab, bsum, bcnt, total;           // byte offsets
 };
@@ -459,11 +393,11 @@ static inline LsLayout ls_layout(size_t B, size_t F, size_t L, size_t T) {
   const size_t rows = B * F, P = L * T;
   LsLayout o;
   o.hdr = 0;
-  o.acc = ls_align256(rows * LS_HDR * sizeof(float));
-  o.bsum = o.acc + ls_align256(rows * P * LS_ACC * sizeof(int));
-  o.bcnt = o.bsum + ls_align256(rows * P * 2 * sizeof(unsigned long long));
-  o.slab = o.bcnt + ls_align256(rows * P * 2 * sizeof(int));
-  o.total = o.slab + ls_align256(rows * L * sizeof(int));
+  o.acc = align256(rows * LS_HDR * sizeof(float));
+  o.bsum = o.acc + align256(rows * P * LS_ACC * sizeof(int));
+  o.bcnt = o.bsum + align256(rows * P * 2 * sizeof(unsigned long long));
+  o.slab = o.bcnt + align256(rows * P * 2 * sizeof(int));
+  o.total = o.slab + align256(rows * L * sizeof(int));
   return o;
 }
 
@@ -513,7 +447,7 @@ extern "C" int s4g_local_search_f32(const float* points_bf3, const float* frames
   hipLaunchKernelGGL(ls_setup_kernel, per_frame, dim3(64), 0, st, points_bf3, frames_bf33, tables_3l2t, (int)F, p,
                      frame_count_b, hdr, acc, slab, bsum, bcnt);
   S4G_LAUNCH_CHECK();
-  const dim3 grid(LS_GX, (unsigned)ls_chunks(N), (unsigned)B);
+  const dim3 grid(LS_GX, (unsigned)sweep_chunks(N, LS_CHUNK_POINTS, LS_MIN_CHUNKS, LS_MAX_CHUNKS), (unsigned)B);
   hipLaunchKernelGGL(ls_scan_kernel, grid, dim3(256), 0, st, xyz_b3n, (const int*)labels_bn, (const float*)hdr,
                      tables_3l2t, (int)N, (int)F, p, slab, acc, frame_count_b);
   S4G_LAUNCH_CHECK();
@@ -524,7 +458,7 @@ extern "C" int s4g_local_search_f32(const float* points_bf3, const float* frames
                      (const int*)acc, (const unsigned long long*)bsum, (const int*)bcnt, (int)F, p, (int*)ints_bfp6,
                      scores_bfp, (int*)slab_bfl, (int*)valid_bf);
   S4G_LAUNCH_CHECK();
-  hipLaunchKernelGGL(ls_compact_kernel, dim3((unsigned)B), dim3(256), 0, st, (const int*)valid_bf, (int)F,
+  hipLaunchKernelGGL(compact_valid_kernel<KeepNonZero>, dim3((unsigned)B), dim3(256), 0, st, (const int*)valid_bf, (int)F,
                      (int*)valid_index_bf, count_b);
   S4G_LAUNCH_CHECK();
   return S4G_OK;

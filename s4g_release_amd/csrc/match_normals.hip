@@ -135,9 +135,6 @@ __global__ __launch_bounds__(MN_BUILD_THREADS) void match_order_kernel(const flo
   ws.rec[i] = make_float4(p0[j], p0[M + j], p0[2 * (size_t)M + j], __int_as_float((int)j));
 }
 
-__device__ __forceinline__ bool mn_finite(float v) { return fabsf(v) <= 3.402823466e38f; }
-__device__ __forceinline__ bool mn_finite(double v) { return fabs(v) <= 1.7976931348623157e308; }
-
 // A wave's running selection: `list` holds n distinct keys, every one below `thr`; once max_nn keys have been seen
 // thr is the max_nn-th smallest of them, so a key at or above it can never be kept.
 struct MnSelect {
@@ -203,7 +200,7 @@ __global__ __launch_bounds__(MN_THREADS) void match_query_kernel(
   const float* __restrict__ p0 = scene + (size_t)b * 3 * M;
   const float* __restrict__ n0 = NEAREST ? nullptr : scene_normals + (size_t)b * 3 * M;
   const float x = q0[q], y = q0[N + q], z = q0[2 * (size_t)N + q];
-  const bool q_ok = mn_finite(x) && mn_finite(y) && mn_finite(z);
+  const bool q_ok = finite(x) && finite(y) && finite(z);
   MnSelect s;
   s.list = lists[wave];
   s.thr = ~0ull;
@@ -272,7 +269,7 @@ __global__ __launch_bounds__(MN_THREADS) void match_query_kernel(
     const uint32_t j = (uint32_t)s.list[lane];
     if (j < (uint32_t)M) {   // (cannot be otherwise: the index is the scene's own)
       const float fx = n0[j], fy = n0[M + j], fz = n0[2 * (size_t)M + j];
-      bad = !(mn_finite(fx) && mn_finite(fy) && mn_finite(fz));
+      bad = !(finite(fx) && finite(fy) && finite(fz));
       ax = (double)fx; ay = (double)fy; az = (double)fz;
     }
   }
@@ -298,7 +295,7 @@ __global__ __launch_bounds__(MN_THREADS) void match_query_kernel(
   if (orient) {
     const float* __restrict__ c0 = camera + (size_t)b * 3;
     const double rx = (double)c0[0] - (double)x, ry = (double)c0[1] - (double)y, rz = (double)c0[2] - (double)z;
-    if (mn_finite(rx) && mn_finite(ry) && mn_finite(rz)) {   // no reference direction otherwise: n stays
+    if (finite(rx) && finite(ry) && finite(rz)) {   // no reference direction otherwise: n stays
       if (nx == 0.0 && ny == 0.0 && nz == 0.0) {
         const double rl = sqrt(rx * rx + ry * ry + rz * rz);   // differences of fp32 numbers: no overflow in double
         if (rl > 0.0) {

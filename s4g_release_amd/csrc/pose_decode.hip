@@ -15,7 +15,7 @@
 // Two tiny HBM-bound kernels around a top-K selection, so only K poses per
 // scene (K * 18 floats) instead of 21 channels x N points leave the GPU / go
 // into the all-gather.
-#include "s4g_common.h"
+#include "frame_sweep.h"
 
 namespace s4g {
 
@@ -161,8 +161,8 @@ constexpr int COLL_GX = 16;        // workgroups that share a scene's pose list 
 constexpr int COLL_U = 4;          // points per lane held in registers while the workgroup's poses pass over them
 constexpr int COLL_SLOTS = 32;     // poses per pass (their matrices and counters live in LDS)
 
-// Points outer, poses inner: a workgroup keeps 1 024 points in registers and runs ALL its poses over them before it
-// loads the next 1 024 -- the cloud is read once per workgroup instead of once per pose.  (Round 6: with one workgroup
+// The cloud sweep of frame_sweep.h, points outer, poses inner: a workgroup keeps 1 024 points in registers and runs ALL
+// its poses over them before it loads the next 1 024 -- the cloud is read once per workgroup instead of once per pose.  (Round 6: with one workgroup
 // per pose every candidate re-read the whole 48 902-point cloud from L2: ~500 candidates per scene x 16 scenes x 587 KB
 // = 4.8 GB per call, 0.5 ms of a pipelined step.)
 __global__ __launch_bounds__(256) void collision_counts_kernel(
@@ -170,40 +170,24 @@ __global__ __launch_bounds__(256) void collision_counts_kernel(
     int* __restrict__ counts, const int64_t* __restrict__ pose_count, int invert_se3) {
   __shared__ float gl[COLL_SLOTS][12];
   __shared__ int cnt[COLL_SLOTS][2];
-  const int b = blockIdx.z, chunk = blockIdx.y, t = threadIdx.x, lane = t & 63;
+  const int b = blockIdx.z, t = threadIdx.x, lane = t & 63;
   const float* px = xyz + (size_t)b * 3 * N;
-  const int nc = (N + COLL_CHUNKS - 1) / COLL_CHUNKS;
-  const int i_lo = chunk * nc, i_hi = min(N, i_lo + nc);
-  // an empty chunk (whenever 7 * nc >= N the last chunk(s) get no points: N = 1..7, 9..14, ..., 49): nothing to count;
-  // `counts` is pre-zeroed by the launcher.  chunk = blockIdx.y, so the exit is workgroup-uniform (before any barrier).
-  if (i_lo >= i_hi) return;
-  int kmax = K;
-  if (pose_count) kmax = (int)min((int64_t)K, max((int64_t)0, pose_count[b]));   // padding rows: never scanned (counts pre-zeroed)
+  const ChunkRange rg = chunk_range(N);
+  if (rg.empty()) return;                            // nothing to count: `counts` is pre-zeroed by the launcher
+  const int kmax = frame_rows(pose_count, b, K);     // padding rows: never scanned (counts pre-zeroed)
   // this workgroup's poses: k = blockIdx.x + COLL_GX * j, j = 0, 1, ... ; COLL_SLOTS of them per pass
   for (int j0 = 0; blockIdx.x + COLL_GX * j0 < kmax; j0 += COLL_SLOTS) {
     __syncthreads();                                  // (the previous pass's tables have been read)
     if (t < COLL_SLOTS) {
       const int k = blockIdx.x + COLL_GX * (j0 + t);
       cnt[t][0] = cnt[t][1] = 0;
-      if (k < kmax) {
-        load_g2l(g2l + ((size_t)b * K + k) * 16, invert_se3, gl[t]);   // row-major 4x4 (s4g_common.h)
-      }
+      if (k < kmax) load_g2l(g2l + ((size_t)b * K + k) * 16, invert_se3, gl[t]);   // row-major 4x4
     }
     __syncthreads();
-    const int left = (kmax - 1 - (int)blockIdx.x) / COLL_GX + 1 - j0;     // poses of this workgroup from j0 on
-    const int nslot = left < COLL_SLOTS ? left : COLL_SLOTS;
-    for (int i0 = i_lo + t; i0 < i_hi + 256 * (COLL_U - 1); i0 += 256 * COLL_U) {
-      float x[COLL_U], y[COLL_U], z[COLL_U];
-      bool in[COLL_U];
-#pragma unroll
-      for (int u = 0; u < COLL_U; ++u) {
-        const int i = i0 + 256 * u;
-        in[u] = i < i_hi;
-        const int ii = in[u] ? i : i_hi - 1;         // masked lanes load the chunk's last point (always < N)
-        x[u] = px[ii];
-        y[u] = px[N + ii];
-        z[u] = px[2 * (size_t)N + ii];
-      }
+    const int nslot = pass_slots(kmax, COLL_GX, j0, COLL_SLOTS);
+    for (int i0 = rg.lo + t; i0 < sweep_end<COLL_U>(rg.hi); i0 += 256 * COLL_U) {
+      PointBlock<COLL_U> pt;
+      pt.load(px, N, i0, rg.hi);
       for (int sl = 0; sl < nslot; ++sl) {
         float gm[12];
 #pragma unroll
@@ -211,9 +195,9 @@ __global__ __launch_bounds__(256) void collision_counts_kernel(
         int nback = 0, nfing = 0;
 #pragma unroll
         for (int u = 0; u < COLL_U; ++u) {
-          const GripperRegions r = gripper_regions(gm, x[u], y[u], z[u], g);
-          nback += __popcll(__ballot(in[u] && r.back));      // wave-uniform
-          nfing += __popcll(__ballot(in[u] && r.fing));
+          const GripperRegions r = gripper_regions(gm, pt.x[u], pt.y[u], pt.z[u], g);
+          nback += __popcll(__ballot(pt.in[u] && r.back));      // wave-uniform
+          nfing += __popcll(__ballot(pt.in[u] && r.fing));
         }
         if (lane == 0) {
           if (nback) atomicAdd(&cnt[sl][0], nback);

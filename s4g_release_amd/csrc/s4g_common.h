@@ -143,56 +143,8 @@ __device__ __forceinline__ int mask_rank(uint64_t mask) {
       (uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0));
 }
 
-// ---- gripper box against a cloud: shared by collision_counts_kernel (pose_decode.hip) and the frame grading
-// (eval_frames.hip), so that the counts behind the palm / in the fingers are the same integers by construction ------
-struct GripperBox {
-  float finger_length, bottom_length, half_hand_thickness, half_bottom_width, half_bottom_space,
-      back_margin;
-};
-
-// rows 0..2 of a pose row's global -> local matrix G (row-major 4x4) as 12 floats (row-major 3x4)
-__device__ __forceinline__ void load_g2l(const float* __restrict__ G, int invert_se3, float* __restrict__ o) {
-  float g00 = G[0], g01 = G[1], g02 = G[2], g03 = G[3];
-  float g10 = G[4], g11 = G[5], g12 = G[6], g13 = G[7];
-  float g20 = G[8], g21 = G[9], g22 = G[10], g23 = G[11];
-  if (invert_se3) {
-    // the matrix is the POSE (gripper -> global): its analytic SE(3) inverse [R^T | -R^T t] in fp32
-    // (torch_batch_transformation_inv, utils/math_utils.py:26-40, as grasp_detector.py:219 calls it) -- formed
-    // here instead of by a batched 3x3 library GEMM per call (0.26 ms for 16 x 2 048 poses)
-    const float tx = g03, ty = g13, tz = g23;
-    const float r01 = g01, r02 = g02, r12 = g12;
-    g01 = g10; g02 = g20; g12 = g21;
-    g10 = r01; g20 = r02; g21 = r12;
-    g03 = -__fadd_rn(__fadd_rn(__fmul_rn(g00, tx), __fmul_rn(g01, ty)), __fmul_rn(g02, tz));
-    g13 = -__fadd_rn(__fadd_rn(__fmul_rn(g10, tx), __fmul_rn(g11, ty)), __fmul_rn(g12, tz));
-    g23 = -__fadd_rn(__fadd_rn(__fmul_rn(g20, tx), __fmul_rn(g21, ty)), __fmul_rn(g22, tz));
-  }
-  o[0] = g00; o[1] = g01; o[2] = g02; o[3] = g03;
-  o[4] = g10; o[5] = g11; o[6] = g12; o[7] = g13;
-  o[8] = g20; o[9] = g21; o[10] = g22; o[11] = g23;
-}
-
-// the regions of view_collision_checker.py:39-60 / eval_point_cloud.py:70-97 for one point; every inequality strict,
-// fp32, each op rounded on its own (these translation units are compiled with -ffp-contract=off)
-struct GripperRegions {
-  bool back, fing, closer;
-  float ly;
-};
-__device__ __forceinline__ GripperRegions gripper_regions(const float* __restrict__ g, float x, float y, float z,
-                                                          const GripperBox& p) {
-  const float lx = g[0] * x + g[1] * y + g[2] * z + g[3];
-  const float ly = g[4] * x + g[5] * y + g[6] * z + g[7];
-  const float lz = g[8] * x + g[9] * y + g[10] * z + g[11];
-  const bool close = (lx < p.finger_length) && (lx > -p.bottom_length);                    // :39-40 / :70-71
-  const bool zin = (lz < p.half_hand_thickness) && (lz > -p.half_hand_thickness);          // :44-45 / :75-76
-  GripperRegions r;
-  r.back = close && zin && (ly < p.half_bottom_width) && (ly > -p.half_bottom_width) && (lx < -p.back_margin);   // :47-49
-  const bool fl = (ly < p.half_bottom_width) && (ly > p.half_bottom_space);                // :54-55
-  const bool fr = (ly > -p.half_bottom_width) && (ly < -p.half_bottom_space);              // :56-57
-  r.fing = close && zin && (fl || fr);                                                      // :59-60
-  r.closer = close && zin && (ly < p.half_bottom_space) && (ly > -p.half_bottom_space);    // eval_point_cloud.py:95-97
-  r.ly = ly;
-  return r;
-}
+// true for every value that is neither NaN nor an infinity
+__device__ __forceinline__ bool finite(float v) { return fabsf(v) <= 3.402823466e38f; }
+__device__ __forceinline__ bool finite(double v) { return fabs(v) <= 1.7976931348623157e308; }
 
 }  // namespace s4g

@@ -346,6 +346,62 @@ def se3_inverse(poses):
     return out.contiguous()
 
 
+_ABSENT = object()     # (an entry point without scene normals; None is a caller's value and is checked like any other)
+
+
+def _dense_scene(scene_points, scene_labels, scene_normals=_ABSENT, same_device=(), size="N", nonempty=False):
+    """The dense scene the frame-grading entry points share, checked in one place: scene_points (B, 3, size) fp32,
+    scene_labels (B, size) int32 and, where the entry point takes them, scene_normals like the points, all on the
+    device of `same_device`, the (name, CUDA tensor) pairs the message names first.
+    -> (xyz, nrm or None, lab, B, size, device), contiguous.  The checks run in this order, before the caller's own
+    checks of its other tensors: a call that is wrong in two arguments may name the other one first."""
+    xyz = _F._f32c(scene_points, "scene_points")
+    nrm = None if scene_normals is _ABSENT else _F._f32c(scene_normals, "scene_normals")
+    if not isinstance(scene_labels, torch.Tensor) or scene_labels.device.type != "cuda":
+        raise RuntimeError("scene_labels must be a CUDA tensor (there is no CPU fallback)")
+    if scene_labels.dtype != torch.int32:
+        raise RuntimeError("scene_labels must be int32, got %s" % scene_labels.dtype)
+    if xyz.dim() != 3 or xyz.size(1) != 3 or (nonempty and xyz.size(2) < 1):
+        raise RuntimeError("scene_points must be (B, 3, %s)" % size)
+    B, _, N = xyz.shape
+    if nrm is not None and tuple(nrm.shape) != (B, 3, N):
+        raise RuntimeError("scene_normals must be (B, 3, %s) like scene_points" % size)
+    if tuple(scene_labels.shape) != (B, N):
+        raise RuntimeError("scene_labels must be (B, %s)" % size)
+    named = list(same_device) + [("scene_points", xyz)] + ([] if nrm is None else [("scene_normals", nrm)]) + \
+        [("scene_labels", scene_labels)]
+    if len({t.device for _, t in named}) != 1:
+        names = [n for n, _ in named]
+        raise RuntimeError("%s and %s must live on one device" % (", ".join(names[:-1]), names[-1]))
+    return xyz, nrm, scene_labels.contiguous(), B, N, xyz.device
+
+
+def _scene_count(count, B, device, name):
+    """The optional per-scene row count `name` (B,) -> int64 on the device, or None."""
+    if count is None:
+        return None
+    if tuple(count.shape) != (B,):
+        raise RuntimeError("%s must be (B,)" % name)
+    return count.to(device=device, dtype=torch.int64).contiguous()
+
+
+def _g2l_of(poses, inverse):
+    """`inverse=` of the pose entry points -> (the matrices the kernel reads, its invert_se3 flag).  "se3": the poses
+    themselves, the kernel forms [R^T | -R^T t] (one launch; a batched library GEMM of 3x3 blocks took 0.26 ms);
+    "general": their float64 inverse rounded to fp32."""
+    if inverse not in ("general", "se3"):
+        raise ValueError("inverse must be 'general' or 'se3'")
+    if inverse == "se3":
+        return poses.float().contiguous(), 1
+    return torch.linalg.inv(poses.double()).float().contiguous(), 0
+
+
+def _workspace(nbytes, device):
+    """What a `*_workspace_bytes` call returned -> (uint8 tensor of that many bytes, at least one; the byte count as int):
+    the two workspace arguments of the entry point."""
+    return torch.empty((max(int(nbytes), 1),), dtype=torch.uint8, device=device), int(nbytes)
+
+
 def view_non_collision(poses, scene_points, gripper=None, inverse="general", count=None):
     """Batched `CloudCollisionChecker.view_non_collision`
     (cloud_processor/view_collision_checker.py:37-65) for all poses of all scenes
@@ -359,23 +415,21 @@ def view_non_collision(poses, scene_points, gripper=None, inverse="general", cou
     xyz = _F._f32c(scene_points, "scene_points")
     B, _, N = xyz.shape
     K = poses.shape[1]
-    if inverse not in ("general", "se3"):
-        raise ValueError("inverse must be 'general' or 'se3'")
-    # inverse="se3": the kernel forms [R^T | -R^T t] itself (one launch; a batched library GEMM of 3x3 blocks took 0.26 ms)
-    g2l = poses.float().contiguous() if inverse == "se3" else torch.linalg.inv(poses.double()).float().contiguous()
+    g2l, invert = _g2l_of(poses, inverse)
     counts = torch.empty((B, K, 2), dtype=torch.int32, device=xyz.device)
     params = (ctypes.c_float * 6)(gripper.finger_length, gripper.bottom_length,
                                   gripper.half_hand_thickness, gripper.half_bottom_width,
                                   gripper.half_bottom_space, gripper.back_collision_margin)
     with torch.cuda.device(xyz.device):
-        if count is None and inverse != "se3":
+        if count is None and not invert:
             rc = _cabi.lib().s4g_collision_counts_f32(xyz.data_ptr(), g2l.data_ptr(), B, N, K, params,
                                                       counts.data_ptr(), _F._stream())
         else:
+            # (not `_scene_count`, nor `_dense_scene` above: this entry point has never checked these shapes)
             cnt = None if count is None else count.to(device=xyz.device, dtype=torch.int64).contiguous()
             rc = _cabi.lib().s4g_collision_counts_n_f32(xyz.data_ptr(), g2l.data_ptr(), B, N, K, params,
-                                                        None if cnt is None else cnt.data_ptr(),
-                                                        1 if inverse == "se3" else 0, counts.data_ptr(), _F._stream())
+                                                        None if cnt is None else cnt.data_ptr(), invert,
+                                                        counts.data_ptr(), _F._stream())
     _cabi.check(rc, "collision_counts")
     ok = (counts[..., 0] <= gripper.back_collision_threshold) & \
          (counts[..., 1] <= gripper.finger_collision_threshold)
@@ -420,49 +474,25 @@ def eval_frames(poses, scene_points, scene_normals, scene_labels, gripper=None, 
     Normals and labels are inputs, as for the reference, which reads them from a file: normal estimation (open3d),
     the baseline variant eval_point_cloud_baseline.py and data_gen/ are out of scope."""
     gripper = gripper or GripperConfig()
-    xyz = _F._f32c(scene_points, "scene_points")
-    nrm = _F._f32c(scene_normals, "scene_normals")
-    if not isinstance(scene_labels, torch.Tensor) or scene_labels.device.type != "cuda":
-        raise RuntimeError("scene_labels must be a CUDA tensor (there is no CPU fallback)")
-    if scene_labels.dtype != torch.int32:
-        raise RuntimeError("scene_labels must be int32, got %s" % scene_labels.dtype)
     if not isinstance(poses, torch.Tensor) or poses.device.type != "cuda":
         raise RuntimeError("poses must be a CUDA tensor (there is no CPU fallback)")
-    if xyz.dim() != 3 or xyz.size(1) != 3:
-        raise RuntimeError("scene_points must be (B, 3, N)")
-    B, _, N = xyz.shape
-    if tuple(nrm.shape) != (B, 3, N):
-        raise RuntimeError("scene_normals must be (B, 3, N) like scene_points")
-    if tuple(scene_labels.shape) != (B, N):
-        raise RuntimeError("scene_labels must be (B, N)")
+    xyz, nrm, lab, B, N, dev = _dense_scene(scene_points, scene_labels, scene_normals, [("poses", poses)])
     if poses.dim() != 4 or poses.size(0) != B or tuple(poses.shape[2:]) != (4, 4):
         raise RuntimeError("poses must be (B, K, 4, 4)")
-    if len({xyz.device, nrm.device, scene_labels.device, poses.device}) != 1:
-        raise RuntimeError("poses, scene_points, scene_normals and scene_labels must live on one device")
-    if inverse not in ("general", "se3"):
-        raise ValueError("inverse must be 'general' or 'se3'")
+    g2l, invert = _g2l_of(poses, inverse)
     K = poses.shape[1]
-    dev = xyz.device
-    lab = scene_labels.contiguous()
-    g2l = poses.float().contiguous() if inverse == "se3" else torch.linalg.inv(poses.double()).float().contiguous()
-    cnt = None
-    if count is not None:
-        if tuple(count.shape) != (B,):
-            raise RuntimeError("count must be (B,)")
-        cnt = count.to(device=dev, dtype=torch.int64).contiguous()
+    cnt = _scene_count(count, B, dev, "count")
     ints = torch.empty((B, K, 8), dtype=torch.int32, device=dev)
     floats = torch.empty((B, K, 5), dtype=torch.float32, device=dev)
     params = (ctypes.c_float * 10)(gripper.finger_length, gripper.bottom_length, gripper.half_hand_thickness,
                                    gripper.half_bottom_width, gripper.half_bottom_space, gripper.back_collision_margin,
                                    gripper.back_collision_threshold, gripper.finger_collision_threshold,
                                    gripper.close_region_min_points, gripper.neighbor_depth)
-    nbytes = _cabi.lib().s4g_eval_frames_workspace_bytes(B, N, K)
-    ws = torch.empty((max(int(nbytes), 1),), dtype=torch.uint8, device=dev)
+    ws, nbytes = _workspace(_cabi.lib().s4g_eval_frames_workspace_bytes(B, N, K), dev)
     with torch.cuda.device(dev):
         rc = _cabi.lib().s4g_eval_frames_f32(xyz.data_ptr(), nrm.data_ptr(), lab.data_ptr(), g2l.data_ptr(), B, N, K,
-                                             params, None if cnt is None else cnt.data_ptr(),
-                                             1 if inverse == "se3" else 0, ints.data_ptr(), floats.data_ptr(),
-                                             ws.data_ptr(), int(nbytes), _F._stream())
+                                             params, None if cnt is None else cnt.data_ptr(), invert,
+                                             ints.data_ptr(), floats.data_ptr(), ws.data_ptr(), nbytes, _F._stream())
     _cabi.check(rc, "eval_frames")
     return FrameEvaluation(ints, floats)
 
@@ -622,33 +652,17 @@ def grade_local_search(points, frames, scene_points, scene_normals, scene_labels
     if unbatched:
         points, frames = points[None], frames[None]
         scene_points, scene_normals, scene_labels = scene_points[None], scene_normals[None], scene_labels[None]
-    xyz = _F._f32c(scene_points, "scene_points")
-    nrm = _F._f32c(scene_normals, "scene_normals")
-    if scene_labels.dtype != torch.int32:
-        raise RuntimeError("scene_labels must be int32, got %s" % scene_labels.dtype)
+    xyz, nrm, lab, B, N, dev = _dense_scene(scene_points, scene_labels, scene_normals,
+                                            [("points", points), ("frames", frames)])
     if points.dtype != torch.float32 or frames.dtype != torch.float32:
         raise RuntimeError("points and frames must be float32")
-    if xyz.dim() != 3 or xyz.size(1) != 3:
-        raise RuntimeError("scene_points must be (B, 3, N)")
-    B, _, N = xyz.shape
-    if tuple(nrm.shape) != (B, 3, N):
-        raise RuntimeError("scene_normals must be (B, 3, N) like scene_points")
-    if tuple(scene_labels.shape) != (B, N):
-        raise RuntimeError("scene_labels must be (B, N)")
     if points.dim() != 3 or points.size(0) != B or points.size(2) != 3:
         raise RuntimeError("points must be (B, F, 3)")
     F = points.shape[1]
     if tuple(frames.shape) != (B, F, 3, 3):
         raise RuntimeError("frames must be (B, F, 3, 3)")
-    if len({xyz.device, nrm.device, scene_labels.device, points.device, frames.device}) != 1:
-        raise RuntimeError("points, frames, scene_points, scene_normals and scene_labels must live on one device")
-    dev = xyz.device
-    pts, frm, lab = points.contiguous(), frames.contiguous(), scene_labels.contiguous()
-    cnt = None
-    if frame_count is not None:
-        if tuple(frame_count.shape) != (B,):
-            raise RuntimeError("frame_count must be (B,)")
-        cnt = frame_count.to(device=dev, dtype=torch.int64).contiguous()
+    pts, frm = points.contiguous(), frames.contiguous()
+    cnt = _scene_count(frame_count, B, dev, "frame_count")
     L, T = cfg.shape
     tb = cfg.tables()
     tables = _small_on_device(torch.cat([tb["depth"], tb["lo"], tb["hi"], tb["cos"], tb["sin"]]), torch.float32, dev)
@@ -663,14 +677,13 @@ def grade_local_search(points, frames, scene_points, scene_normals, scene_labels
                                    cfg.finger_collision_threshold, cfg.close_region_min_points, cfg.neighbor_depth,
                                    cfg.table_height, cfg.table_height + cfg.table_collision_offset,
                                    cfg.num_points_threshold)
-    nbytes = _cabi.lib().s4g_local_search_workspace_bytes(B, N, F, L, T)
-    ws = torch.empty((max(int(nbytes), 1),), dtype=torch.uint8, device=dev)
+    ws, nbytes = _workspace(_cabi.lib().s4g_local_search_workspace_bytes(B, N, F, L, T), dev)
     with torch.cuda.device(dev):
         rc = _cabi.lib().s4g_local_search_f32(pts.data_ptr(), frm.data_ptr(), xyz.data_ptr(), nrm.data_ptr(),
                                               lab.data_ptr(), B, N, F, L, T, params, int(cfg.no_label),
                                               tables.data_ptr(), None if cnt is None else cnt.data_ptr(),
                                               ints.data_ptr(), scores.data_ptr(), slab.data_ptr(), valid.data_ptr(),
-                                              valid_index.data_ptr(), count.data_ptr(), ws.data_ptr(), int(nbytes),
+                                              valid_index.data_ptr(), count.data_ptr(), ws.data_ptr(), nbytes,
                                               _F._stream())
     _cabi.check(rc, "local_search")
     return LocalSearch(ints, scores, slab, valid, valid_index, count, pts, frm, cfg, unbatched)
@@ -765,11 +778,8 @@ def estimate_frames(cloud, normals, frame_index=None, frame_count=None, radius=C
             raise RuntimeError("frame_index must be int32, got %s" % frame_index.dtype)
         if frame_index.dim() != 2 or frame_index.size(0) != B:
             raise RuntimeError("frame_index must be (B, F)")
-        index, cnt = frame_index.contiguous(), None
-        if frame_count is not None:
-            if tuple(frame_count.shape) != (B,):
-                raise RuntimeError("frame_count must be (B,)")
-            cnt = frame_count.to(device=dev, dtype=torch.int64).contiguous()
+        index = frame_index.contiguous()
+        cnt = _scene_count(frame_count, B, dev, "frame_count")
     if len({xyz.device, nrm.device, index.device}) != 1:
         raise RuntimeError("cloud, normals and frame_index must live on one device")
     F = index.shape[1]
@@ -777,13 +787,12 @@ def estimate_frames(cloud, normals, frame_index=None, frame_count=None, radius=C
     points = torch.empty((B, F, 3), dtype=torch.float32, device=dev)
     count = torch.empty((B, F), dtype=torch.int32, device=dev)
     flags = torch.empty((B, F), dtype=torch.int32, device=dev)
-    nbytes = _cabi.lib().s4g_darboux_frames_workspace_bytes(B, N, F)
-    ws = torch.empty((max(int(nbytes), 1),), dtype=torch.uint8, device=dev)
+    ws, nbytes = _workspace(_cabi.lib().s4g_darboux_frames_workspace_bytes(B, N, F), dev)
     with torch.cuda.device(dev):
         rc = _cabi.lib().s4g_darboux_frames_f32(xyz.data_ptr(), nrm.data_ptr(), index.data_ptr(),
                                                 None if cnt is None else cnt.data_ptr(), B, N, F, float(radius),
                                                 int(min_neighbours), frames.data_ptr(), points.data_ptr(),
-                                                count.data_ptr(), flags.data_ptr(), ws.data_ptr(), int(nbytes),
+                                                count.data_ptr(), flags.data_ptr(), ws.data_ptr(), nbytes,
                                                 _F._stream())
     _cabi.check(rc, "darboux_frames")
     return DarbouxFrames(frames, points, count, flags, index, cnt, unbatched)
@@ -876,13 +885,12 @@ def match_normals(cloud, scene_points, scene_normals, camera=None, radius=CURVAT
     normals = torch.empty((B, 3, N), dtype=torch.float32, device=dev)
     count = torch.empty((B, N), dtype=torch.int32, device=dev)
     flags = torch.empty((B, N), dtype=torch.int32, device=dev)
-    nbytes = _cabi.lib().s4g_match_normals_workspace_bytes(B, N, M)
-    ws = torch.empty((max(int(nbytes), 1),), dtype=torch.uint8, device=dev)
+    ws, nbytes = _workspace(_cabi.lib().s4g_match_normals_workspace_bytes(B, N, M), dev)
     with torch.cuda.device(dev):
         rc = _cabi.lib().s4g_match_normals_f32(xyz.data_ptr(), pts.data_ptr(), nrm.data_ptr(),
                                                None if cam is None else cam.data_ptr(), B, N, M, float(radius),
                                                int(max_nn), normals.data_ptr(), count.data_ptr(), flags.data_ptr(),
-                                               ws.data_ptr(), int(nbytes), _F._stream())
+                                               ws.data_ptr(), nbytes, _F._stream())
     _cabi.check(rc, "match_normals")
     return MatchedNormals(normals, count, flags, unbatched)
 
@@ -1033,28 +1041,15 @@ def grade_contact_frames(global_to_local, scene_points, scene_labels, config=Non
     unbatched = global_to_local.dim() == 3
     if unbatched:
         global_to_local, scene_points, scene_labels = global_to_local[None], scene_points[None], scene_labels[None]
-    xyz = _F._f32c(scene_points, "scene_points")
-    if scene_labels.dtype != torch.int32:
-        raise RuntimeError("scene_labels must be int32, got %s" % scene_labels.dtype)
+    xyz, _, lab, B, M, dev = _dense_scene(scene_points, scene_labels, same_device=[("global_to_local", global_to_local)],
+                                          size="M", nonempty=True)
     if global_to_local.dtype != torch.float32:
         raise RuntimeError("global_to_local must be float32")
-    if xyz.dim() != 3 or xyz.size(1) != 3 or xyz.size(2) < 1:
-        raise RuntimeError("scene_points must be (B, 3, M)")
-    B, _, M = xyz.shape
-    if tuple(scene_labels.shape) != (B, M):
-        raise RuntimeError("scene_labels must be (B, M)")
     if global_to_local.dim() != 4 or global_to_local.size(0) != B or tuple(global_to_local.shape[2:]) != (4, 4):
         raise RuntimeError("global_to_local must be (B, F, 4, 4)")
-    if len({xyz.device, scene_labels.device, global_to_local.device}) != 1:
-        raise RuntimeError("global_to_local, scene_points and scene_labels must live on one device")
-    dev = xyz.device
     F = global_to_local.shape[1]
-    g2l, lab = global_to_local.contiguous(), scene_labels.contiguous()
-    cnt = None
-    if frame_count is not None:
-        if tuple(frame_count.shape) != (B,):
-            raise RuntimeError("frame_count must be (B,)")
-        cnt = frame_count.to(device=dev, dtype=torch.int64).contiguous()
+    g2l = global_to_local.contiguous()
+    cnt = _scene_count(frame_count, B, dev, "frame_count")
     nz, ny, nx = cfg.shape
     P = cfg.placements
     tb = cfg.tables()
@@ -1068,14 +1063,13 @@ def grade_contact_frames(global_to_local, scene_points, scene_labels, config=Non
                                    max(abs(float(v)) for v in cfg.length_search),
                                    max(abs(float(v)) for v in cfg.width_search),
                                    max(abs(float(v)) for v in cfg.height_search))
-    nbytes = _cabi.lib().s4g_contact_search_workspace_bytes(B, M, F, P)
-    ws = torch.empty((max(int(nbytes), 1),), dtype=torch.uint8, device=dev)
+    ws, nbytes = _workspace(_cabi.lib().s4g_contact_search_workspace_bytes(B, M, F, P), dev)
     with torch.cuda.device(dev):
         rc = _cabi.lib().s4g_contact_search_f32(g2l.data_ptr(), xyz.data_ptr(), lab.data_ptr(), B, M, F, nz, ny, nx,
                                                 params, int(cfg.no_label), tables.data_ptr(),
                                                 None if cnt is None else cnt.data_ptr(), ints.data_ptr(),
                                                 table.data_ptr(), valid.data_ptr(), label.data_ptr(), fail.data_ptr(),
-                                                ws.data_ptr(), int(nbytes), _F._stream())
+                                                ws.data_ptr(), nbytes, _F._stream())
     _cabi.check(rc, "contact_search")
     return ContactSearch(ints, table, valid, label, fail, g2l, cnt, cfg, unbatched)
 
@@ -1105,11 +1099,10 @@ def match_nearest(cloud, scene_points, radius=CURVATURE_RADIUS):
         raise RuntimeError("cloud and scene_points must live on one device")
     M = pts.size(2)
     nearest = torch.empty((B, N), dtype=torch.int32, device=xyz.device)
-    nbytes = _cabi.lib().s4g_match_normals_workspace_bytes(B, N, M)
-    ws = torch.empty((max(int(nbytes), 1),), dtype=torch.uint8, device=xyz.device)
+    ws, nbytes = _workspace(_cabi.lib().s4g_match_normals_workspace_bytes(B, N, M), xyz.device)
     with torch.cuda.device(xyz.device):
         rc = _cabi.lib().s4g_match_nearest_f32(xyz.data_ptr(), pts.data_ptr(), B, N, M, float(radius),
-                                               nearest.data_ptr(), ws.data_ptr(), int(nbytes), _F._stream())
+                                               nearest.data_ptr(), ws.data_ptr(), nbytes, _F._stream())
     _cabi.check(rc, "match_nearest")
     return nearest
 
@@ -1264,11 +1257,7 @@ def label_contact_view(reference_cloud, cloud, scene_points, scene_normals, came
         frame_count = search.frame_count
     if tuple(search.valid_i32.shape) != (B, F) or search.valid_i32.device != dev:
         raise RuntimeError("search must hold the (B, F) frames of frame_point_index, on the same device")
-    cnt = None
-    if frame_count is not None:
-        if tuple(frame_count.shape) != (B,):
-            raise RuntimeError("frame_count must be (B,)")
-        cnt = frame_count.to(device=dev, dtype=torch.int64)
+    cnt = _scene_count(frame_count, B, dev, "frame_count")
     nearest = match_nearest(ref, pts, radius)
     offsets, order = frames_by_point(frame_point_index, M, cnt)
     normals = torch.empty((B, 3, N), dtype=torch.float32, device=dev)
