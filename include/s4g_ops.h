@@ -66,7 +66,9 @@ extern "C" {
  *     s4g_match_normals_workspace_bytes (the scene normals a view's points take over in front of those frames);
  *     s4g_contact_search_f32 / s4g_contact_search_workspace_bytes (the contact model's grading of every scene frame),
  *     s4g_match_nearest_f32 (the nearest scene point of every view point) and s4g_contact_select_f32 (the contact
- *     model's per-view-point normal and best frame). */
+ *     model's per-view-point normal and best frame); s4g_best_placement_f32 (the best placement of that search per
+ *     frame and its global -> local matrix), s4g_close_region_f32 / s4g_close_region_workspace_bytes (the packed
+ *     close-region point sets and 12-channel projection maps the GPD and PointNetGPD baselines read). */
 #define S4G_ABI_VERSION 14
 
 /* ---------------------------------------------------------------------------
@@ -769,6 +771,57 @@ int s4g_local_search_f32(const float *points_bf3, const float *frames_bf33, cons
                          const int64_t *frame_count_b, int32_t *ints_bfp6, float *scores_bfp, int32_t *slab_bfl,
                          int32_t *valid_bf, int32_t *valid_index_bf, int64_t *count_b, void *workspace,
                          size_t workspace_bytes, s4g_stream_t stream);
+
+/* Baseline inputs (csrc/close_region.hip): TorchBaseLineSingleViewPointCloud.finger_hand's best placement and crop
+ * (data_gen/pcd_classes/torch_baseline_single_view_point_cloud.py:220-331), close_region_projection (:334-393) and the
+ * crop of torch_precomputed_baseline.py:350-383, without host synchronisation.
+ *
+ * s4g_best_placement_f32: points (B, F, 3), frames (B, F, 3, 3) (axes as COLUMNS), scores (B, F, L * T) and tables_3l2t
+ * as s4g_local_search_f32 reads and writes them.  Per frame, over the L * T placements in flattened order, the first
+ * one whose score is > 0 and > every earlier score (a NaN is never taken, :308-312); the frame is valid unless that
+ * score is < 1e-4 (:323).
+ *   index_bf       int32 (B, F): the placement, -1 where the frame is invalid;  score_bf fp32 (B, F): its score (0 where
+ *                  no placement was taken)
+ *   g2l_bf44       fp32 (B, F, 4, 4) = LOCAL_TO_LOCAL_SEARCH[index] @ [R^T | -R^T p] (`baseline_frame`, :320-322), formed
+ *                  directly in fp32; all 0 where the frame is invalid
+ *   valid_index_bf int32 (B, F): the valid frames in ascending order, then -1;  count_b int64 (B): how many
+ * B, F <= 65 535, 1 <= L <= 8, 1 <= T <= 16.
+ *
+ * s4g_close_region_f32: g2l (B, F, 4, 4) global -> local matrices (rows 0..2 are read), xyz / normals (B, 3, N) fp32.
+ * live_bf (device int32 (B, F), may be NULL): rows with 0 are not scanned; frame_count_b (device, may be NULL): rows at
+ * or past frame_count_b[b] are not scanned.  Such rows read count 0, flags 0 and zero maps.
+ * params13 (HOST pointer) = {x_lo, x_hi, HALF_BOTTOM_SPACE, HALF_HAND_THICKNESS, unit x, y, z, h0 x, y, z, hstep x, y, z}.
+ * A point is a member of a frame's close region iff x_lo < lx < x_hi, |ly| < params[2] and |lz| < params[3] for
+ * l = G[0..2] . (x, y, z, 1) in fp32, each operation rounded on its own; every inequality strict.
+ *   count_bf     int32 (B, F): the members; exact whatever the capacity
+ *   offset_bf1   int64 (B, F + 1): the exclusive scan of count in frame order
+ *   points_b3c / normals_b3c fp32 (B, 3, capacity), index_bc int32 (B, capacity): frame f's set is the slice
+ *                offset[f] : offset[f + 1], in ASCENDING SCENE-POINT INDEX (the order of the reference's boolean
+ *                indexing): (lx, ly + params[2], lz + params[3]) (:314-315), the rotation of G applied to the normal, and
+ *                the source point index.  Storage past the last stored frame is left untouched.
+ *   flags_bf     int32 (B, F): bit 0 = the set does not fit (offset[f + 1] > capacity): nothing is stored for the frame;
+ *                bit 1 = a kept point or normal is not finite.  Either bit: the frame's maps are 0.
+ *   maps_bf12rr  fp32 (B, F, 12, R, R), 2 <= R <= 64.  Voxel per axis a = floor(c / unit[a]), an fp32 division; a point
+ *                counts iff all three indices are in [0, R).  Per voxel: the mean normal (sum / count) and occupancy
+ *                (count > 0).  For the axis orders i = 0, 1, 2 = (x, y, z), (y, z, x), (z, x, y) the map is indexed by the
+ *                first two axes and summed along the third: channel 4 i = the mean of h0 + k * hstep over the occupied
+ *                voxels k of the line (torch.linspace(unit / 2, dim - unit / 2, R)[k], :379-381), channels 4 i + 1 ..
+ *                4 i + 3 = the sum of the voxel means over the line divided by the number of occupied voxels; a pixel
+ *                without an occupied voxel is 0 (:377-391).
+ * Run-to-run bit-identical and batch invariant: counts are integers, the per-voxel normal sums are integers of scale
+ * 2^-30 (each component clamped to [-4, 4]) added with integer atomics, everything after them runs in a fixed order.
+ * B, F <= 65 535, N < 2^31 - 2048, capacity < 2^31.  Workspace: s4g_close_region_workspace_bytes(B, N, F, capacity)
+ * bytes, 256-byte aligned; contents need not be initialised. */
+int s4g_best_placement_f32(const float *points_bf3, const float *frames_bf33, const float *scores_bfp,
+                           const float *tables_3l2t, int64_t B, int64_t F, int64_t L, int64_t T, int32_t *index_bf,
+                           float *score_bf, float *g2l_bf44, int32_t *valid_index_bf, int64_t *count_b,
+                           s4g_stream_t stream);
+size_t s4g_close_region_workspace_bytes(int64_t B, int64_t N, int64_t F, int64_t capacity);
+int s4g_close_region_f32(const float *g2l_bf44, const float *xyz_b3n, const float *normals_b3n,
+                         const int32_t *live_bf, const int64_t *frame_count_b, int64_t B, int64_t N, int64_t F,
+                         int64_t capacity, int64_t R, const float *params13, int32_t *count_bf, int64_t *offset_bf1,
+                         float *points_b3c, float *normals_b3c, int32_t *index_bc, float *maps_bf12rr,
+                         int32_t *flags_bf, void *workspace, size_t workspace_bytes, s4g_stream_t stream);
 
 /* Darboux frames of the data generator's label search (csrc/darboux.hip): TorchSingleViewPointCloud._estimate_frame
  * (data_gen/pcd_classes/torch_single_view_point_cloud.py:107-133) for every frame row of every scene, without host

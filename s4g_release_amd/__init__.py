@@ -56,3 +56,23 @@ def label_contact_view(*args, **kwargs):
     fold over the graded scene frames in one call.  See `postprocess.label_contact_view`."""
     from .postprocess import label_contact_view as _label
     return _label(*args, **kwargs)
+
+
+def best_placement(*args, **kwargs):
+    """The baseline data generator's best placement per frame of a `LocalSearch`.  See `postprocess.best_placement`."""
+    from .postprocess import best_placement as _best
+    return _best(*args, **kwargs)
+
+
+def close_regions(*args, **kwargs):
+    """The packed close-region point sets and 12-channel projection maps of every frame of every scene in one call: the
+    inputs of PointNetGPD and GPD.  See `postprocess.close_regions`."""
+    from .postprocess import close_regions as _regions
+    return _regions(*args, **kwargs)
+
+
+def label_baseline_view(*args, **kwargs):
+    """Frames in, baseline inputs out: `grade_local_search` without the label gate, `best_placement` and
+    `close_regions` in one call.  See `postprocess.label_baseline_view`."""
+    from .postprocess import label_baseline_view as _label
+    return _label(*args, **kwargs)

@@ -121,6 +121,10 @@ SIGNATURES = {
     "s4g_local_search_f32": (_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64,
                                     ctypes.POINTER(ctypes.c_float), _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                     _sz, _vp]),
+    "s4g_best_placement_f32": (_int, [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "s4g_close_region_workspace_bytes": (_sz, [_i64, _i64, _i64, _i64]),
+    "s4g_close_region_f32": (_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64,
+                                    ctypes.POINTER(ctypes.c_float), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "s4g_darboux_frames_workspace_bytes": (_sz, [_i64, _i64, _i64]),
     "s4g_darboux_frames_f32": (_int, [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _f32, _i32, _vp, _vp, _vp, _vp, _vp, _sz,
                                       _vp]),

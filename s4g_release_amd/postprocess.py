@@ -1273,3 +1273,237 @@ def label_contact_view(reference_cloud, cloud, scene_points, scene_normals, came
                                                 count.data_ptr(), _F._stream())
     _cabi.check(rc, "contact_select")
     return ContactLabels(nearest, normals, best, score, valid_index, count, search, xyz, ss, aps, unbatched)
+
+
+CR_MAX_RESOLUTION = 64                     # the compiled maximum of csrc/close_region.hip
+CR_DEFAULT_POINTS_PER_FRAME = 4096         # the default capacity is F * min(N, this)
+
+
+@dataclass
+class ProjectionConfig:
+    """PROJECTION_RESOLUTION and PROJECTION_MARGIN (data_gen/configs/config.py:93-94).  The box the maps cover comes from
+    the gripper constants (torch_baseline_single_view_point_cloud.py:11-13): x = FINGER_LENGTH, y = 2 * HALF_BOTTOM_SPACE,
+    z = 2 * HALF_HAND_THICKNESS."""
+    resolution: int = 60
+    margin: int = 1
+
+    def check(self):
+        if not (2 <= int(self.resolution) <= CR_MAX_RESOLUTION):
+            raise ValueError("resolution must be 2..%d, got %r" % (CR_MAX_RESOLUTION, self.resolution))
+        if not (0 <= self.margin < self.resolution):
+            raise ValueError("margin must be in [0, resolution)")
+
+    @staticmethod
+    def dims(gripper=None):
+        g = gripper or LocalSearchConfig()
+        return (g.finger_length, g.half_bottom_space * 2, g.half_hand_thickness * 2)
+
+    def units(self, gripper=None):
+        """dim / (resolution - margin) per axis in Python floats (:16-18), rounded to fp32 once."""
+        return tuple(float(torch.tensor(d / (self.resolution - self.margin), dtype=torch.float32))
+                     for d in self.dims(gripper))
+
+    def heights(self, gripper=None):
+        """(h0, hstep) per axis, fp32 values: the height of voxel k is h0 + k * hstep =
+        torch.linspace(unit / 2, dim - unit / 2, resolution)[k] (:379-381), which is (k + 0.5) * unit when margin is 0."""
+        out = []
+        for d in self.dims(gripper):
+            u = d / (self.resolution - self.margin)
+            out.append((float(torch.tensor(0.5 * u, dtype=torch.float32)),
+                        float(torch.tensor((d - u) / (self.resolution - 1), dtype=torch.float32))))
+        return tuple(out)
+
+
+@dataclass
+class BestPlacement:
+    """What `best_placement` returns: `index` (B, F) int32 (-1 where the frame is invalid), `score` (B, F),
+    `global_to_local` (B, F, 4, 4) (the reference's `baseline_frame`, 0 where invalid), `valid_index` (B, F) ascending
+    and -1 padded, `count` (B,) int64."""
+    index: torch.Tensor
+    score: torch.Tensor
+    global_to_local: torch.Tensor
+    valid_index: torch.Tensor
+    count: torch.Tensor
+    unbatched: bool = False
+
+    valid = property(lambda self: self.index >= 0)
+
+
+def best_placement(search):
+    """The fold of `TorchBaseLineSingleViewPointCloud.finger_hand` (torch_baseline_single_view_point_cloud.py:308-312,
+    323-331) over a `LocalSearch`: per frame, over the L * T placements in flattened order, the first one whose
+    antipodal score is > 0 and > every earlier score (a NaN is never taken); the frame is valid unless that score is
+    < 1e-4.  -> `BestPlacement`; `global_to_local` = LOCAL_TO_LOCAL_SEARCH[index] @ [R^T | -R^T p], formed directly in fp32."""
+    if not isinstance(search, LocalSearch):
+        raise RuntimeError("best_placement takes the LocalSearch that grade_local_search returns")
+    scores = search.scores
+    if scores.device.type != "cuda":
+        raise RuntimeError("search must hold CUDA tensors (there is no CPU fallback)")
+    dev = scores.device
+    B, F, L, T = scores.shape
+    tb = search.config.tables()
+    tables = _small_on_device(torch.cat([tb["depth"], tb["lo"], tb["hi"], tb["cos"], tb["sin"]]), torch.float32, dev)
+    index = torch.empty((B, F), dtype=torch.int32, device=dev)
+    score = torch.empty((B, F), dtype=torch.float32, device=dev)
+    g2l = torch.empty((B, F, 4, 4), dtype=torch.float32, device=dev)
+    valid_index = torch.empty((B, F), dtype=torch.int32, device=dev)
+    count = torch.empty((B,), dtype=torch.int64, device=dev)
+    sc = scores.contiguous()
+    with torch.cuda.device(dev):
+        rc = _cabi.lib().s4g_best_placement_f32(search.points.data_ptr(), search.frames.data_ptr(), sc.data_ptr(),
+                                                tables.data_ptr(), B, F, L, T, index.data_ptr(), score.data_ptr(),
+                                                g2l.data_ptr(), valid_index.data_ptr(), count.data_ptr(), _F._stream())
+    _cabi.check(rc, "best_placement")
+    return BestPlacement(index, score, g2l, valid_index, count, search.unbatched)
+
+
+@dataclass
+class CloseRegions:
+    """What `close_regions` returns.  `count` (B, F) int32, `offset` (B, F + 1) int64, `points` / `normals`
+    (B, 3, capacity), `index` (B, capacity) int32, `maps` (B, F, 12, R, R), `flags` (B, F) int32 (bit 0: the set does
+    not fit; bit 1: a kept point or normal is not finite).  Frame f's set is the slice offset[f]:offset[f + 1]."""
+    count: torch.Tensor
+    offset: torch.Tensor
+    points: torch.Tensor
+    normals: torch.Tensor
+    index: torch.Tensor
+    maps: torch.Tensor
+    flags: torch.Tensor
+    unbatched: bool = False
+
+    def sets(self, b=0, frames=None):
+        """The lists of the reference's `dump()` (:195-197) for the frames `frames` of scene b (default: every frame
+        with flags 0): (close_region_points_set, close_region_normals_set, close_region_projection_map_set) as lists of
+        numpy arrays (3, n), (3, n), (12, R, R).  Reads the counts on the host."""
+        off = self.offset[b].cpu().tolist()
+        fl = self.flags[b].cpu().tolist()
+        if frames is None:
+            frames = [f for f in range(len(fl)) if fl[f] == 0]
+        P, Nn, M = self.points[b].cpu().numpy(), self.normals[b].cpu().numpy(), self.maps[b].cpu().numpy()
+        frames = [int(f) for f in frames]
+        keep = [(off[f], off[f + 1]) if not (fl[f] & 1) else (0, 0) for f in frames]
+        return ([P[:, lo:hi].copy() for lo, hi in keep], [Nn[:, lo:hi].copy() for lo, hi in keep],
+                [M[f].copy() for f in frames])
+
+
+def close_regions(global_to_local, cloud, normals, gripper=None, x_range=None, live=None, frame_count=None,
+                  capacity=None, projection=None):
+    """The crop and `close_region_projection` of the baselines' data generators
+    (torch_baseline_single_view_point_cloud.py:294-318,334-393; torch_precomputed_baseline.py:350-383) for every frame
+    of every scene in one sync-free, graph-capturable call -> `CloseRegions`.
+
+    global_to_local (B, F, 4, 4) fp32 (`BestPlacement.global_to_local`); cloud, normals (B, 3, N) fp32; unbatched inputs
+    get a leading 1.  Rows with live == 0 (live (B, F), optional) or at or past frame_count[b] (optional) are not
+    scanned: count 0, flags 0, zero maps.  A point is in the region iff x_lo < lx < x_hi, |ly| < half_bottom_space and
+    |lz| < half_hand_thickness, every inequality strict, the bounds rounded to fp32 once.  x_range defaults to
+    (-bottom_length, finger_length), the baseline class, whose depth slab is the only x filter; (0, finger_length) is
+    the precomputed class's box.  `gripper` is any object with finger_length, bottom_length, half_bottom_space and
+    half_hand_thickness (default `LocalSearchConfig()`); `projection` a `ProjectionConfig`.  capacity (points per scene
+    in the packed buffers) defaults to F * min(N, 4096) and must be below 2^31; `count` and `offset` are exact whatever
+    it is, a frame whose set does not fit is flagged and not stored.  Normal components are clamped to [-4, 4] in the
+    maps' voxel sums (fixed point, as the band sums of `grade_local_search`)."""
+    g = gripper or LocalSearchConfig()
+    proj = projection or ProjectionConfig()
+    proj.check()
+    for name, t in (("global_to_local", global_to_local), ("cloud", cloud), ("normals", normals)):
+        if not isinstance(t, torch.Tensor) or t.device.type != "cuda":
+            raise RuntimeError("%s must be a CUDA tensor (there is no CPU fallback)" % name)
+        if t.dtype != torch.float32:
+            raise RuntimeError("%s must be float32" % name)
+    unbatched = global_to_local.dim() == 3
+    if unbatched:
+        global_to_local, cloud, normals = global_to_local[None], cloud[None], normals[None]
+        live = None if live is None else live[None]
+    if cloud.dim() != 3 or cloud.size(1) != 3 or cloud.size(2) < 1:
+        raise RuntimeError("cloud must be (B, 3, N)")
+    B, _, N = cloud.shape
+    if tuple(normals.shape) != (B, 3, N):
+        raise RuntimeError("normals must be (B, 3, N) like cloud")
+    if global_to_local.dim() != 4 or global_to_local.size(0) != B or tuple(global_to_local.shape[2:]) != (4, 4):
+        raise RuntimeError("global_to_local must be (B, F, 4, 4)")
+    if len({global_to_local.device, cloud.device, normals.device}) != 1:
+        raise RuntimeError("global_to_local, cloud and normals must live on one device")
+    dev = cloud.device
+    F = global_to_local.shape[1]
+    if live is not None:
+        if not isinstance(live, torch.Tensor) or live.device != dev or tuple(live.shape) != (B, F):
+            raise RuntimeError("live must be a (B, F) tensor on the device of cloud")
+        live = live.to(torch.int32).contiguous()
+    cnt = _scene_count(frame_count, B, dev, "frame_count")
+    capacity = F * min(N, CR_DEFAULT_POINTS_PER_FRAME) if capacity is None else int(capacity)
+    if not (0 <= capacity < 2 ** 31):
+        raise ValueError("capacity must be in [0, 2^31), got %d" % capacity)
+    x_lo, x_hi = (-g.bottom_length, g.finger_length) if x_range is None else x_range
+    units, heights = proj.units(g), proj.heights(g)
+    params = (ctypes.c_float * 13)(x_lo, x_hi, g.half_bottom_space, g.half_hand_thickness, *units,
+                                   *[h[0] for h in heights], *[h[1] for h in heights])
+    R = int(proj.resolution)
+    G, xyz, nrm = global_to_local.contiguous(), cloud.contiguous(), normals.contiguous()
+    count = torch.empty((B, F), dtype=torch.int32, device=dev)
+    offset = torch.empty((B, F + 1), dtype=torch.int64, device=dev)
+    points = torch.empty((B, 3, capacity), dtype=torch.float32, device=dev)
+    out_n = torch.empty((B, 3, capacity), dtype=torch.float32, device=dev)
+    index = torch.empty((B, capacity), dtype=torch.int32, device=dev)
+    maps = torch.empty((B, F, 12, R, R), dtype=torch.float32, device=dev)
+    flags = torch.empty((B, F), dtype=torch.int32, device=dev)
+    ws, nbytes = _workspace(_cabi.lib().s4g_close_region_workspace_bytes(B, N, F, capacity), dev)
+    with torch.cuda.device(dev):
+        rc = _cabi.lib().s4g_close_region_f32(G.data_ptr(), xyz.data_ptr(), nrm.data_ptr(),
+                                              None if live is None else live.data_ptr(),
+                                              None if cnt is None else cnt.data_ptr(), B, N, F, capacity, R, params,
+                                              count.data_ptr(), offset.data_ptr(), points.data_ptr(), out_n.data_ptr(),
+                                              index.data_ptr(), maps.data_ptr(), flags.data_ptr(), ws.data_ptr(), nbytes,
+                                              _F._stream())
+    _cabi.check(rc, "close_region")
+    return CloseRegions(count, offset, points, out_n, index, maps, flags, unbatched)
+
+
+@dataclass
+class BaselineLabels:
+    """What `label_baseline_view` returns: the `LocalSearch` (without the label gate), its `BestPlacement` and the
+    `CloseRegions` of the best placements."""
+    search: LocalSearch
+    best: BestPlacement
+    regions: CloseRegions
+
+    def dump(self, b=0):
+        """The dictionary of the reference's `dump()` (torch_baseline_single_view_point_cloud.py:189-198) for scene b, in
+        the world frame (the camera transform is the caller's); `point_cloud` holds the frame origins (3, F).  Reads the
+        counts on the host."""
+        n = int(self.best.count[b])
+        vi = self.best.valid_index[b, :n].long()
+        pts, nrm, maps = self.regions.sets(b, vi.cpu().tolist())
+        return {"antipodal_score": self.best.score[b, vi].cpu().numpy(),
+                "point_cloud": self.search.points[b].t().contiguous().cpu().numpy(),
+                "valid_index": vi.int().cpu().numpy(),
+                "baseline_frame": self.best.global_to_local[b, vi].cpu().numpy(),
+                "close_region_points_set": pts, "close_region_normals_set": nrm,
+                "close_region_projection_map_set": maps}
+
+
+def label_baseline_view(points, frames, scene_points, scene_normals, cloud=None, normals=None, config=None,
+                        projection=None, frame_count=None, x_range=None, capacity=None):
+    """`run_score` of `TorchBaseLineSingleViewPointCloud` (torch_baseline_single_view_point_cloud.py:158-181,220-331) as
+    one sync-free call -> `BaselineLabels`: `grade_local_search` with one label for every scene point (which removes
+    the label gate, the only difference between the two searches), `best_placement`, then `close_regions` of `cloud` /
+    `normals` (default: the scene itself, as in that class) in the best placement of every valid frame.  The
+    reference's stop after `grasp_num` valid frames is the caller's slice of `best.valid_index`; no stale slots, as in
+    `grade_local_search`.  `TorchPrecomputedBaselinePointCloud`'s crop and maps are x_range=(0, finger_length) with the
+    view as `cloud`; its lookup of precomputed scene scores stays out of scope."""
+    cfg = config or LocalSearchConfig()
+    if not isinstance(scene_points, torch.Tensor) or scene_points.device.type != "cuda":
+        raise RuntimeError("scene_points must be a CUDA tensor (there is no CPU fallback)")
+    if (cloud is None) != (normals is None):
+        raise RuntimeError("cloud and normals go together")
+    lab_shape = scene_points.shape[:-2] + scene_points.shape[-1:]
+    labels = torch.zeros(lab_shape, dtype=torch.int32, device=scene_points.device)
+    search = grade_local_search(points, frames, scene_points, scene_normals, labels, cfg, frame_count)
+    best = best_placement(search)
+    if cloud is None:
+        cloud, normals = scene_points, scene_normals
+    if search.unbatched and cloud.dim() == 2:
+        cloud, normals = cloud[None], normals[None]
+    regions = close_regions(best.global_to_local, cloud, normals, cfg, x_range, best.index >= 0, frame_count, capacity,
+                            projection)
+    regions.unbatched = search.unbatched
+    return BaselineLabels(search, best, regions)
