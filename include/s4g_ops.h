@@ -68,7 +68,9 @@ extern "C" {
  *     s4g_match_nearest_f32 (the nearest scene point of every view point) and s4g_contact_select_f32 (the contact
  *     model's per-view-point normal and best frame); s4g_best_placement_f32 (the best placement of that search per
  *     frame and its global -> local matrix), s4g_close_region_f32 / s4g_close_region_workspace_bytes (the packed
- *     close-region point sets and 12-channel projection maps the GPD and PointNetGPD baselines read). */
+ *     close-region point sets and 12-channel projection maps the GPD and PointNetGPD baselines read);
+ *     s4g_gpd_pack_f32 / s4g_gpd_pack_bytes / s4g_gpd_forward_f32 / s4g_gpd_workspace_bytes (the GPD baseline's
+ *     classifier on those maps: two 5x5 convolutions with max-pools on the matrix cores and two linear layers). */
 #define S4G_ABI_VERSION 14
 
 /* ---------------------------------------------------------------------------
@@ -822,6 +824,42 @@ int s4g_close_region_f32(const float *g2l_bf44, const float *xyz_b3n, const floa
                          int64_t capacity, int64_t R, const float *params13, int32_t *count_bf, int64_t *offset_bf1,
                          float *points_b3c, float *normals_b3c, int32_t *index_bc, float *maps_bf12rr,
                          int32_t *flags_bf, void *workspace, size_t workspace_bytes, s4g_stream_t stream);
+
+/* GPDClassifier on the 60 x 60 close-region maps (csrc/gpd.hip; added under ABI 14):
+ * inference/grasp_proposal/network_models/models/GPD.py in eval mode, without host synchronisation.  Per image x (Cin, 60, 60):
+ *   p1 = maxpool2x2(conv1(x) + b1)   conv1 Cin -> 20, 5x5, valid, stride 1, cross-correlation   (20, 28, 28)   no ReLU
+ *   p2 = maxpool2x2(conv2(p1) + b2)  conv2 20 -> 50, 5x5                                         (50, 12, 12)   no ReLU
+ *   h  = relu(fc1(flatten(p2)) + c1) flatten order (c, y, x), 7200 -> 500
+ *   logits = fc2(h) + c2             500 -> classes
+ * Pool windows start at even rows and columns.  1 <= Cin <= 12, 1 <= classes <= 16.
+ *
+ * s4g_gpd_pack_f32: the eight parameter tensors (DEVICE pointers, fp32, contiguous, torch's shapes: conv1_w (20, Cin, 5, 5),
+ * conv2_w (50, 20, 5, 5), fc1_w (500, 7200), fc2_w (classes, 500)) -> `packed` (device, s4g_gpd_pack_bytes(Cin, classes)
+ * bytes, 16-byte aligned): the conv and fc1 weights as two power-of-two scaled fp16 planes in MFMA fragment order, the
+ * biases and fc2 in fp32, and the constants the activation scales are formed from.  Pack again when a parameter changes.
+ *
+ * s4g_gpd_forward_f32: maps = image g at maps + g * image_stride + c * channel_stride (in floats), the (60, 60) plane
+ * contiguous; channels 0 .. Cin - 1 are read.  index (device int32 (G), may be NULL = 0 .. G - 1): row g scores image
+ * index[g] of the num_images images; a negative index, or one >= num_images, reads nothing and writes a ZERO row.  With
+ * index NULL, G > num_images is S4G_EINVAL.  The convolutions and fc1 run on v_mfma_f32_32x32x16_f16 in the f16x2 split
+ * (three products per MAC, fp32 accumulate) with power-of-two activation scales PER IMAGE (from the image's own largest
+ * magnitude and bounds formed from it and the weights); fc2 in fp32 FMAs.  Every row is therefore independent of the
+ * other rows, of G, of `chunk` and of the run: batch invariant and bit-reproducible.  An image that holds a NaN or an
+ * infinity in a channel that is read gets NaN in every output row of its own; the other rows do not change.
+ *   logits (G, classes); pool1 (G, 20, 28, 28), pool2 (G, 50, 12, 12), hidden (G, 500): fp32 copies of the levels,
+ *   written only where the pointer is not NULL.
+ * The images are processed `chunk` at a time (0: 1 024; at most 32 768); the workspace is
+ * s4g_gpd_workspace_bytes(min(chunk, G), Cin, classes) bytes (0 stands for 1 024 there too), 16-byte aligned, contents
+ * need not be initialised.  G, num_images < 2^31. */
+size_t s4g_gpd_pack_bytes(int Cin, int classes);
+int s4g_gpd_pack_f32(const float *conv1_w, const float *conv1_b, const float *conv2_w, const float *conv2_b,
+                     const float *fc1_w, const float *fc1_b, const float *fc2_w, const float *fc2_b, int Cin, int classes,
+                     void *packed, s4g_stream_t stream);
+size_t s4g_gpd_workspace_bytes(int64_t chunk, int Cin, int classes);
+int s4g_gpd_forward_f32(const float *maps, int64_t image_stride, int64_t channel_stride, const int32_t *index, int64_t G,
+                        int64_t num_images, const void *packed, int Cin, int classes, int64_t chunk, float *pool1,
+                        float *pool2, float *hidden, float *logits, void *workspace, size_t workspace_bytes,
+                        s4g_stream_t stream);
 
 /* Darboux frames of the data generator's label search (csrc/darboux.hip): TorchSingleViewPointCloud._estimate_frame
  * (data_gen/pcd_classes/torch_single_view_point_cloud.py:107-133) for every frame row of every scene, without host

@@ -76,3 +76,22 @@ def label_baseline_view(*args, **kwargs):
     `close_regions` in one call.  See `postprocess.label_baseline_view`."""
     from .postprocess import label_baseline_view as _label
     return _label(*args, **kwargs)
+
+
+def score_projections(*args, **kwargs):
+    """GPD's grasp logits of the frames of `label_baseline_view`, read from its maps in place.  See
+    `postprocess.score_projections`."""
+    from .postprocess import score_projections as _score
+    return _score(*args, **kwargs)
+
+
+def build_gpd(*args, **kwargs):
+    """The GPD baseline's classifier as a reference-shaped module.  See `baselines.build_gpd`."""
+    from .baselines import build_gpd as _build
+    return _build(*args, **kwargs)
+
+
+def FusedGPD(*args, **kwargs):
+    """`baselines.GPDClassifier` in eval mode on the HIP kernels.  See `baselines.FusedGPD`."""
+    from .baselines import FusedGPD as _Fused
+    return _Fused(*args, **kwargs)

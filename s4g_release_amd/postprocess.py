@@ -1507,3 +1507,29 @@ def label_baseline_view(points, frames, scene_points, scene_normals, cloud=None,
                             projection)
     regions.unbatched = search.unbatched
     return BaselineLabels(search, best, regions)
+
+
+def score_projections(labels_or_regions, runner, grasp_num=None):
+    """The GPD baseline's classifier on the maps of `label_baseline_view`, still on the device and without a gathered
+    copy: `runner` (a `baselines.FusedGPD`) reads `regions.maps` in place through
+    `best.valid_index[:, :grasp_num]` -> logits (B, K, classes), K = min(grasp_num, F); rows at or past `best.count[b]`
+    are zero.  The reference's stop after `grasp_num` valid frames is the slice.  Given `CloseRegions` alone, every
+    frame is scored -> (B, F, classes)."""
+    if isinstance(labels_or_regions, BaselineLabels):
+        regions, best = labels_or_regions.regions, labels_or_regions.best
+    elif isinstance(labels_or_regions, CloseRegions):
+        regions, best = labels_or_regions, None
+    else:
+        raise RuntimeError("score_projections takes the BaselineLabels of label_baseline_view or its CloseRegions")
+    if not callable(runner):
+        raise RuntimeError("runner must be a baselines.FusedGPD")
+    if best is None:
+        if grasp_num is not None:
+            raise RuntimeError("grasp_num needs the BaselineLabels (the valid frames are in its best placement)")
+        return runner(regions.maps)
+    index = best.valid_index
+    if grasp_num is not None:
+        if int(grasp_num) < 0:
+            raise ValueError("grasp_num must be >= 0, got %r" % (grasp_num,))
+        index = index[:, :int(grasp_num)]
+    return runner(regions.maps, index=index)
