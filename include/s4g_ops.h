@@ -70,7 +70,10 @@ extern "C" {
  *     frame and its global -> local matrix), s4g_close_region_f32 / s4g_close_region_workspace_bytes (the packed
  *     close-region point sets and 12-channel projection maps the GPD and PointNetGPD baselines read);
  *     s4g_gpd_pack_f32 / s4g_gpd_pack_bytes / s4g_gpd_forward_f32 / s4g_gpd_workspace_bytes (the GPD baseline's
- *     classifier on those maps: two 5x5 convolutions with max-pools on the matrix cores and two linear layers). */
+ *     classifier on those maps: two 5x5 convolutions with max-pools on the matrix cores and two linear layers);
+ *     s4g_pngpd_pack_f32 / s4g_pngpd_pack_bytes / s4g_pngpd_forward_f32 / s4g_pngpd_workspace_bytes (the PointNetGPD
+ *     baseline's classifier on the packed close-region point sets, or on dense (G, 3, n) sets: two per-point trunks
+ *     with a segment maximum and the per-set layers on the matrix cores). */
 #define S4G_ABI_VERSION 14
 
 /* ---------------------------------------------------------------------------
@@ -860,6 +863,54 @@ int s4g_gpd_forward_f32(const float *maps, int64_t image_stride, int64_t channel
                         int64_t num_images, const void *packed, int Cin, int classes, int64_t chunk, float *pool1,
                         float *pool2, float *hidden, float *logits, void *workspace, size_t workspace_bytes,
                         s4g_stream_t stream);
+
+/* PointNetClassifier on variable-length point sets (csrc/pointnet_gpd.hip; added under ABI 14):
+ * inference/grasp_proposal/network_models/models/PointNetGPD.py in eval mode with every BatchNorm folded into its layer by
+ * the caller, without host synchronisation, every launch on `stream`.  Per set x (3, n), n >= 1:
+ *   stn_global = max_j relu(W3 relu(W2 relu(W1 x_j + b1) + b2) + b3)      feat.stn.conv1..3: 3 -> 64 -> 128 -> 1024
+ *   trans      = fc3(relu(fc2(relu(fc1(stn_global))))) + I                feat.stn.fc1..3: 1024 -> 512 -> 256 -> 9, (3, 3)
+ *   global     = max_j (V3 relu(V2 relu(V1 trans^T x_j + c1) + c2) + c3)  feat.conv1..3, NO ReLU after the last layer
+ *   hidden     = relu(fc2(relu(fc1(global))))                             fc1, fc2: 1024 -> 512 -> 256
+ *   logits     = fc3(hidden)                                              256 -> classes, 1 <= classes <= 16
+ *
+ * s4g_pngpd_pack_f32: weights12 / biases12 are HOST arrays of twelve DEVICE pointers (fp32, contiguous, torch's
+ * (out, in) shapes, kernel-size-1 convolutions as (out, in)) in the order feat.stn.conv1, conv2, conv3, fc1, fc2, fc3,
+ * feat.conv1, conv2, conv3, fc1, fc2, fc3 -> `packed` (device, s4g_pngpd_pack_bytes(classes) bytes, 16-byte aligned):
+ * the 64 -> 128, 128 -> 1024, 1024 -> 512 and 512 -> 256 weights as two power-of-two scaled fp16 planes in MFMA fragment
+ * order, the rest in fp32, and the constants the activation scales are formed from.  Pack again when a parameter changes.
+ *
+ * s4g_pngpd_forward_f32: point j, coordinate c of source set s lies at points + base[s] + c * channel_stride + j (floats):
+ *   dense  (offset == NULL): base[s] = s * set_stride, every set holds n_points points; num_sets sets;
+ *   packed (offset != NULL): s = b * F + f, base[s] = b * set_stride + offset[b * (F + 1) + f], count[s] points
+ *          (offset int64 (B, F + 1), count int32 (B, F), flags int32 (B, F) or NULL: the fields of s4g_close_region_f32),
+ *          num_sets = B * F, capacity = the points per scene the buffer holds.
+ * index (device int32 (G), may be NULL = 0 .. G - 1): row g scores source set index[g].  With index NULL, G > num_sets is
+ * S4G_EINVAL.  status (G) int32, may be NULL:
+ *   0  scored;
+ *   1  the set holds a NaN or an infinity: every output row of it is NaN, nothing of it is staged, no other row changes;
+ *   2  not scored: index negative or >= num_sets, no points, flags bit 0, or a slice that leaves [0, capacity): ZERO rows
+ *      (the reference raises on an empty set; the zero row is this library's decision).
+ * The four matrix layers named above and both trunks' 64 -> 128 and 128 -> 1024 layers run on v_mfma_f32_32x32x16_f16 in
+ * the f16x2 split (three products per MAC, fp32 accumulate); the 3 -> 64 and 256 -> 9 / classes layers in fp32 FMAs in a
+ * fixed order.  The transform is folded into a per-set first layer V1 trans^T; the 64- and 128-wide per-point
+ * intermediates stay in LDS.  A tile is 128 points of one set; the tile list is scanned on the device from the counts;
+ * the segment maximum merges tiles with integer atomicMax on an order-preserving key: exact and order independent.
+ * Power-of-two scales PER SET.  Every row is independent of the other rows, of G, of `chunk`, of the input form and of
+ * the run: batch invariant and bit-reproducible.
+ *   logits (G, classes); stn_global (G, 1024), trans (G, 3, 3), global_feat (G, 1024), hidden (G, 256): fp32 copies of
+ *   the levels, written only where the pointer is not NULL.
+ * The sets are processed `chunk` at a time (0: 1 024; at most 32 768); the workspace is
+ * s4g_pngpd_workspace_bytes(min(chunk, G), classes) bytes (0 stands for 1 024 there too), 16-byte aligned, contents
+ * need not be initialised.  G, num_sets, n_points, capacity < 2^31. */
+size_t s4g_pngpd_pack_bytes(int classes);
+int s4g_pngpd_pack_f32(const float *const *weights12, const float *const *biases12, int classes, void *packed,
+                       s4g_stream_t stream);
+size_t s4g_pngpd_workspace_bytes(int64_t chunk, int classes);
+int s4g_pngpd_forward_f32(const float *points, int64_t set_stride, int64_t channel_stride, int64_t n_points,
+                          const int64_t *offset, const int32_t *count, const int32_t *flags, int64_t F, int64_t capacity,
+                          const int32_t *index, int64_t G, int64_t num_sets, const void *packed, int classes,
+                          int64_t chunk, float *stn_global, float *trans, float *global_feat, float *hidden,
+                          int32_t *status, float *logits, void *workspace, size_t workspace_bytes, s4g_stream_t stream);
 
 /* Darboux frames of the data generator's label search (csrc/darboux.hip): TorchSingleViewPointCloud._estimate_frame
  * (data_gen/pcd_classes/torch_single_view_point_cloud.py:107-133) for every frame row of every scene, without host

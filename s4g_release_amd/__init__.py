@@ -5,6 +5,9 @@ so the importable spelling uses an underscore.)
 
 Importing the package does not touch the GPU and does not load the HIP library;
 the first operator call does, and fails loudly if ``libs4g_hip.so`` is absent.
+
+The baselines' path ends in two consumers of `label_baseline_view`: `score_projections` (GPD on the projection maps)
+and `score_close_regions` (PointNetGPD on the packed close-region point sets, each set whole and at its true size).
 """
 __version__ = "0.1.0"
 
@@ -94,4 +97,23 @@ def build_gpd(*args, **kwargs):
 def FusedGPD(*args, **kwargs):
     """`baselines.GPDClassifier` in eval mode on the HIP kernels.  See `baselines.FusedGPD`."""
     from .baselines import FusedGPD as _Fused
+    return _Fused(*args, **kwargs)
+
+
+def score_close_regions(*args, **kwargs):
+    """PointNetGPD's grasp logits of the frames of `label_baseline_view`, read from its packed point sets in place.
+    See `postprocess.score_close_regions`."""
+    from .postprocess import score_close_regions as _score
+    return _score(*args, **kwargs)
+
+
+def build_pointnetgpd(*args, **kwargs):
+    """The PointNetGPD baseline's classifier as a reference-shaped module.  See `baselines.build_pointnetgpd`."""
+    from .baselines import build_pointnetgpd as _build
+    return _build(*args, **kwargs)
+
+
+def FusedPointNetGPD(*args, **kwargs):
+    """`baselines.PointNetGPDClassifier` in eval mode on the HIP kernels.  See `baselines.FusedPointNetGPD`."""
+    from .baselines import FusedPointNetGPD as _Fused
     return _Fused(*args, **kwargs)

@@ -130,6 +130,11 @@ SIGNATURES = {
     "s4g_gpd_workspace_bytes": (_sz, [_i64, _int, _int]),
     "s4g_gpd_forward_f32": (_int, [_vp, _i64, _i64, _vp, _i64, _i64, _vp, _int, _int, _i64, _vp, _vp, _vp, _vp, _vp, _sz,
                                    _vp]),
+    "s4g_pngpd_pack_bytes": (_sz, [_int]),
+    "s4g_pngpd_pack_f32": (_int, [_vp, _vp, _int, _vp, _vp]),
+    "s4g_pngpd_workspace_bytes": (_sz, [_i64, _int]),
+    "s4g_pngpd_forward_f32": (_int, [_vp, _i64, _i64, _i64, _vp, _vp, _vp, _i64, _i64, _vp, _i64, _i64, _vp, _int, _i64,
+                                     _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "s4g_darboux_frames_workspace_bytes": (_sz, [_i64, _i64, _i64]),
     "s4g_darboux_frames_f32": (_int, [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _f32, _i32, _vp, _vp, _vp, _vp, _vp, _sz,
                                       _vp]),

@@ -1533,3 +1533,29 @@ def score_projections(labels_or_regions, runner, grasp_num=None):
             raise ValueError("grasp_num must be >= 0, got %r" % (grasp_num,))
         index = index[:, :int(grasp_num)]
     return runner(regions.maps, index=index)
+
+
+def score_close_regions(labels_or_regions, runner, grasp_num=None):
+    """The PointNetGPD baseline's classifier on the point sets of `label_baseline_view`, still on the device and without
+    a gathered or sampled copy: `runner` (a `baselines.FusedPointNetGPD`) reads `regions.points` in place through
+    `offset` / `count` / `flags` and `best.valid_index[:, :grasp_num]`, every set whole and at its true size -> logits
+    (B, K, classes), K = min(grasp_num, F); rows at or past `best.count[b]` are zero, and so is the row of a frame whose
+    set is empty or did not fit the capacity.  Given `CloseRegions` alone, every frame is scored -> (B, F, classes)."""
+    if isinstance(labels_or_regions, BaselineLabels):
+        regions, best = labels_or_regions.regions, labels_or_regions.best
+    elif isinstance(labels_or_regions, CloseRegions):
+        regions, best = labels_or_regions, None
+    else:
+        raise RuntimeError("score_close_regions takes the BaselineLabels of label_baseline_view or its CloseRegions")
+    if not callable(runner):
+        raise RuntimeError("runner must be a baselines.FusedPointNetGPD")
+    if best is None:
+        if grasp_num is not None:
+            raise RuntimeError("grasp_num needs the BaselineLabels (the valid frames are in its best placement)")
+        return runner(regions.points, offset=regions.offset, count=regions.count, flags=regions.flags)
+    index = best.valid_index
+    if grasp_num is not None:
+        if int(grasp_num) < 0:
+            raise ValueError("grasp_num must be >= 0, got %r" % (grasp_num,))
+        index = index[:, :int(grasp_num)]
+    return runner(regions.points, offset=regions.offset, count=regions.count, flags=regions.flags, index=index)
