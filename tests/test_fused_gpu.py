@@ -2,7 +2,8 @@
 fused group / interpolate / max / head epilogues).  Unit tests compare each
 loader x epilogue against a plain fp32 torch restatement of the same layer;
 model tests compare against the golden fixtures captured from the reference's
-Python network (1e-4 abs; indices bit-exact)."""
+Python network (1e-4 abs; indices bit-exact).  The tiled single-layer kernels alone, at their tile, column, depth,
+scene and epilogue edges into guarded buffers: tests/test_tiled_edges_gpu.py."""
 import ctypes
 import os
 
