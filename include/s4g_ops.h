@@ -73,7 +73,9 @@ extern "C" {
  *     classifier on those maps: two 5x5 convolutions with max-pools on the matrix cores and two linear layers);
  *     s4g_pngpd_pack_f32 / s4g_pngpd_pack_bytes / s4g_pngpd_forward_f32 / s4g_pngpd_workspace_bytes (the PointNetGPD
  *     baseline's classifier on the packed close-region point sets, or on dense (G, 3, n) sets: two per-point trunks
- *     with a segment maximum and the per-set layers on the matrix cores). */
+ *     with a segment maximum and the per-set layers on the matrix cores); s4g_estimate_normals_f32 /
+ *     s4g_estimate_normals_workspace_bytes (PCA normals of a cloud that has none: the input of all of the above for a
+ *     sensor cloud). */
 #define S4G_ABI_VERSION 14
 
 /* ---------------------------------------------------------------------------
@@ -993,6 +995,46 @@ int s4g_match_normals_f32(const float *query_b3n, const float *scene_b3m, const 
                           const float *camera_b3 /* may be NULL */, int64_t B, int64_t N, int64_t M, float radius,
                           int32_t max_nn, float *normals_b3n, int32_t *count_bn, int32_t *flags_bn,
                           void *workspace, size_t workspace_bytes, s4g_stream_t stream);
+
+/* Normal estimation (csrc/match_normals.hip): PointCloud.estimate_normals of the reference
+ * (data_gen/pcd_classes/pointcloud.py:48-60; the same method in cloud_processor.py:44-52, eval_experiment/pointcloud.py
+ * and data_gen/eval/pointcloud.py) -- open3d's estimate_normals(KDTreeSearchParamHybrid(radius, max_nn),
+ * fast_normal_computation=False), normalize_normals and orient_normals_towards_camera_location -- for every point of
+ * every cloud, without host synchronisation.  cloud (B, 3, N) fp32; camera (B, 3) fp32 the camera LOCATION, or NULL;
+ * live_b (B,) int32 on the device, or NULL: the rows of cloud b at or past live_b[b] (clamped to [0, N]) are padding.
+ * Every live point is a query, and the live finite points are the keys.  Per query p:
+ *   neighbours = every key with squared distance < radius * radius, the rule of s4g_match_normals_f32 (fp32, each op
+ *     rounded on its own, strict); where more than max_nn qualify the max_nn smallest by (fp32 squared distance, index)
+ *     are kept.  The query is its own neighbour at distance 0; its copies at a lower index rank before it;
+ *   d_j = key_j - p in double; S1 = sum d_j, S2 = sum d_j d_j^T in double by a fixed butterfly over the kept keys in
+ *     rank order (no atomics); cov = S2 / k - (S1 / k)(S1 / k)^T, k the number kept;
+ *   n = the unit eigenvector of cov's smallest eigenvalue (cyclic Jacobi in double on cov scaled by its largest entry;
+ *     the lowest column where two eigenvalues are equal);
+ *   sign: with a camera, ref = camera - p in double, n . ref < 0 -> n = -n.  Without a camera, where n . ref is
+ *     exactly 0 and where ref is not finite: the component of n of largest magnitude is positive, the lowest axis
+ *     winning a tie (the rule of s4g_darboux_frames_f32);
+ *   n is rounded to fp32 once.
+ * Decisions (open3d cannot be run where this library is tested; these define the result).  (1) Fewer than 3 kept
+ *   neighbours: (0, 0, 1), then given its sign as above; flags bit 1 (open3d leaves the point's previous normal, (0, 0,
+ *   1) in a cloud that had none).  (2) Every kept point identical, or a solve that gives a zero or non-finite vector:
+ *   (0, 0, 1), given its sign; flags bit 2 (open3d's solver returns the zero vector, which it replaces by (0, 0, 1)).
+ *   Collinear neighbours are not flagged: they get a unit vector perpendicular to their line.  (3) A query that is not
+ *   finite: (0, 0, 1) as it stands, count 0, flags bit 3 alone; a point that is not finite is never a neighbour.
+ *   (4) More than max_nn points inside the radius: flags bit 0.  (5) Padding rows: the zero vector, count 0, flags bit 4
+ *   alone; they are neither queries nor keys.
+ * Outputs: normals_b3n fp32 (B, 3, N); count_bn int32 (B, N) the number of kept neighbours; flags_bn int32 (B, N).
+ * Neighbour grid: that of s4g_match_normals_f32 about the cloud's first live finite point.  A point that is not finite
+ * or is padding is held by no cell and sends no scene to the index-order scan; a finite live point further than about
+ * 4 000 radii from the origin does: the same neighbour sets, ranks and bits either way.  Run-to-run bit-identical and
+ * batch invariant; batches above 256 scenes (fewer where 256 * N >= 2^31) are served in chunks on one workspace.
+ * radius in (0, 1e18), max_nn in [1, 64], N < 2^30, B <= 65 535 (S4G_EINVAL otherwise).
+ * Workspace: s4g_estimate_normals_workspace_bytes(B, N) bytes (S4G_EWORKSPACE below that), 256-byte aligned; contents
+ * need not be initialised. */
+size_t s4g_estimate_normals_workspace_bytes(int64_t B, int64_t N);
+int s4g_estimate_normals_f32(const float *cloud_b3n, const float *camera_b3 /* may be NULL */,
+                             const int32_t *live_b /* may be NULL: all N */, int64_t B, int64_t N, float radius,
+                             int32_t max_nn, float *normals_b3n, int32_t *count_bn, int32_t *flags_bn,
+                             void *workspace, size_t workspace_bytes, s4g_stream_t stream);
 
 /* The nearest scene point of every view point (csrc/match_normals.hip): the max_nn = 1 search of
  * TorchPrecomputedSingleViewPointCloud._find_match (data_gen/pcd_classes/torch_contact_single_view_point_cloud.py:

@@ -40,6 +40,13 @@ def match_normals(*args, **kwargs):
     return _match(*args, **kwargs)
 
 
+def estimate_normals(*args, **kwargs):
+    """The reference's normal estimation (open3d's hybrid-search plane fit, turned towards the camera) for every point
+    of every cloud in one call.  See `postprocess.estimate_normals`."""
+    from .postprocess import estimate_normals as _estimate
+    return _estimate(*args, **kwargs)
+
+
 def label_view(*args, **kwargs):
     """View cloud in, S4G labels out: `match_normals` where asked for, the sampled indices, `estimate_frames` and
     `grade_local_search` in one call.  See `postprocess.label_view`."""

@@ -141,6 +141,8 @@ SIGNATURES = {
     "s4g_match_normals_workspace_bytes": (_sz, [_i64, _i64, _i64]),
     "s4g_match_normals_f32": (_int, [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _f32, _i32, _vp, _vp, _vp, _vp, _sz, _vp]),
     "s4g_match_nearest_f32": (_int, [_vp, _vp, _i64, _i64, _i64, _f32, _vp, _vp, _sz, _vp]),
+    "s4g_estimate_normals_workspace_bytes": (_sz, [_i64, _i64]),
+    "s4g_estimate_normals_f32": (_int, [_vp, _vp, _vp, _i64, _i64, _f32, _i32, _vp, _vp, _vp, _vp, _sz, _vp]),
     "s4g_contact_search_workspace_bytes": (_sz, [_i64, _i64, _i64, _i64]),
     "s4g_contact_search_f32": (_int, [_vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _i64, ctypes.POINTER(ctypes.c_float),
                                       _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),

@@ -404,3 +404,347 @@ extern "C" int s4g_match_nearest_f32(const float* query_b3n, const float* scene_
   return match_run(query_b3n, scene_b3m, nullptr, nullptr, B, N, M, radius, 1, nullptr, nullptr, nullptr, nearest_bn,
                    workspace, workspace_bytes, stream);
 }
+
+// ---------------------------------------------------------------------------------------------------------------
+// Normal estimation (s4g_estimate_normals_f32): PointCloud.estimate_normals of the reference
+// (data_gen/pcd_classes/pointcloud.py:48-60): open3d's hybrid search, the plane fit of the kept neighbours,
+// normalize_normals and orient_normals_towards_camera_location.  The cloud is its own key set: the grid, the sort and
+// MnSelect above serve it unchanged.  What differs from the matching:
+//   - the grid's origin is the first LIVE FINITE point (normals_origin_kernel), and a point that is not finite or lies
+//     at or past live[b] sends no scene to the scan: it is sorted behind every scene of the chunk (scene number Bc in
+//     its key) and counted in no cell, so no query ever reads it;
+//   - the kept points' differences to the query are formed in double, their first and second moments summed by the
+//     butterfly above in rank order, cov = S2 / k - (S1 / k)(S1 / k)^T;
+//   - the eigenvector of the smallest eigenvalue by cyclic Jacobi in double on the matrix scaled by its largest entry
+//     (every lane of the wave holds the same sums and runs the same solve; lane 0 writes).
+// ---------------------------------------------------------------------------------------------------------------
+namespace s4g {
+
+constexpr int EN_SWEEPS = 10;          // cyclic Jacobi in double: quadratic, leaves the loop after 5 to 7 sweeps
+constexpr int EN_FEW = 3;              // fewer kept neighbours than this define no plane
+constexpr int EN_CAPPED = 1, EN_FEWBIT = 2, EN_DEGENERATE = 4, EN_NONFINITE = 8, EN_PADDING = 16;
+
+struct NormalsWs {
+  MatchWs m;
+  float4* origin;                      // [Bc] the first live finite point of every scene (zero where there is none)
+};
+
+static size_t normals_ws(void* base, int64_t Bc, int64_t N, NormalsWs* w) {
+  const size_t off = match_ws(base, Bc, N, w ? &w->m : nullptr);
+  if (w && base) w->origin = (float4*)((char*)base + off);
+  return off + mn_align((size_t)Bc * sizeof(float4));
+}
+
+// scenes one pass serves: as mn_chunk, with one key value (scene number Bc) left for the points no cell holds
+static int64_t normals_chunk(int64_t B, int64_t N) { return mn_chunk(B, N); }
+
+__device__ __forceinline__ int normals_live(const int32_t* __restrict__ live, int b, int N) {
+  if (!live) return N;
+  const int n = live[b];
+  return n < 0 ? 0 : (n > N ? N : n);
+}
+
+// One workgroup per scene: the first live finite point in index order, 256 points at a time.
+__global__ __launch_bounds__(MN_BUILD_THREADS) void normals_origin_kernel(const float* __restrict__ cloud,
+                                                                          const int32_t* __restrict__ live, int N,
+                                                                          float4* __restrict__ origin) {
+  __shared__ int first;
+  const int b = blockIdx.x;
+  const int n = normals_live(live, b, N);
+  const float* __restrict__ p0 = cloud + (size_t)b * 3 * N;
+  if (threadIdx.x == 0) first = 0x7fffffff;
+  __syncthreads();
+  for (int base = 0; base < n; base += MN_BUILD_THREADS) {   // n is the workgroup's: the loop is uniform
+    const int j = base + (int)threadIdx.x;
+    const bool ok = j < n && finite(p0[j]) && finite(p0[N + j]) && finite(p0[2 * (size_t)N + j]);
+    if (__syncthreads_or(ok ? 1 : 0)) {
+      if (ok) atomicMin(&first, j);
+      break;
+    }
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const int j = first;
+    origin[b] = j < n ? make_float4(p0[j], p0[N + j], p0[2 * (size_t)N + j], 0.f) : make_float4(0.f, 0.f, 0.f, 0.f);
+  }
+}
+
+// One thread per point: its sort key and, where it is a key of the search, its cell's population.  A finite live
+// point outside the exactness range sends its scene to the scan (cell 0, as above); a point that is not finite or not
+// live takes scene number Bc and no cell.
+__global__ __launch_bounds__(MN_BUILD_THREADS) void normals_keys_kernel(const float* __restrict__ cloud,
+                                                                        const int32_t* __restrict__ live, int N, int Bc,
+                                                                        float inv_h, NormalsWs ws) {
+  const int b = blockIdx.y;
+  const int j = blockIdx.x * MN_BUILD_THREADS + threadIdx.x;
+  if (j >= N) return;
+  const float* __restrict__ p0 = cloud + (size_t)b * 3 * N;
+  const float4 o = ws.origin[b];
+  const float x = p0[j], y = p0[N + j], z = p0[2 * (size_t)N + j];
+  const size_t i = (size_t)b * N + j;
+  uint32_t key = (uint32_t)Bc << MN_CELL_BITS;
+  if (j < normals_live(live, b, N) && finite(x) && finite(y) && finite(z)) {
+    int cell = 0;
+    if (grid_coord_ok(x, o.x, inv_h) && grid_coord_ok(y, o.y, inv_h) && grid_coord_ok(z, o.z, inv_h))
+      cell = mn_cell(grid_coord(x, o.x, inv_h), grid_coord(y, o.y, inv_h), grid_coord(z, o.z, inv_h));
+    else
+      ws.m.flags[b] = 1;
+    key = ((uint32_t)b << MN_CELL_BITS) | (uint32_t)cell;
+    atomicAdd(&ws.m.count[(size_t)b * MN_CELLS + cell], 1);
+  }
+  ws.m.keys_a[i] = key;
+  ws.m.vals_a[i] = (uint32_t)j;
+}
+
+// One thread per sorted record: the compact copy the queries read.  The scene comes from the sorted key: the records of
+// the points no cell holds lie behind the last scene's and are never read (they are filled all the same).
+__global__ __launch_bounds__(MN_BUILD_THREADS) void normals_order_kernel(const float* __restrict__ cloud, int N, int Bc,
+                                                                         NormalsWs ws) {
+  const int q = blockIdx.x * MN_BUILD_THREADS + threadIdx.x;
+  if (q >= N) return;
+  const size_t i = (size_t)blockIdx.y * N + q;
+  const uint32_t s = ws.m.keys_b[i] >> MN_CELL_BITS, j = ws.m.vals_b[i];
+  const float nan = __int_as_float(0x7fc00000);
+  float4 r = make_float4(nan, nan, nan, __int_as_float(0));
+  if (s < (uint32_t)Bc && j < (uint32_t)N) {
+    const float* __restrict__ p0 = cloud + (size_t)s * 3 * N;
+    r = make_float4(p0[j], p0[N + j], p0[2 * (size_t)N + j], __int_as_float((int)j));
+  }
+  ws.m.rec[i] = r;
+}
+
+// One Jacobi rotation in double, as darboux.hip's in fp32: (p, q) the plane, r the third index, v?p / v?q the columns
+// p and q of the eigenvector matrix.  An off-diagonal too small to turn anything is left alone.
+__device__ __forceinline__ void normals_rotate(double& app, double& aqq, double& apq, double& arp, double& arq,
+                                               double& v0p, double& v0q, double& v1p, double& v1q, double& v2p,
+                                               double& v2q) {
+  if (!(fabs(apq) > 1e-40)) return;
+  const double theta = (aqq - app) / (2.0 * apq);
+  double t = 1.0 / (fabs(theta) + sqrt(theta * theta + 1.0));
+  if (theta < 0.0) t = -t;
+  const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
+  app = app - t * apq;
+  aqq = aqq + t * apq;
+  apq = 0.0;
+  const double rp = c * arp - s * arq, rq = s * arp + c * arq;
+  arp = rp;
+  arq = rq;
+  double a = c * v0p - s * v0q, d = s * v0p + c * v0q;
+  v0p = a; v0q = d;
+  a = c * v1p - s * v1q; d = s * v1p + c * v1q;
+  v1p = a; v1q = d;
+  a = c * v2p - s * v2q; d = s * v2p + c * v2q;
+  v2p = a; v2q = d;
+}
+
+__global__ __launch_bounds__(MN_THREADS) void normals_query_kernel(
+    const float* __restrict__ cloud, const float* __restrict__ camera, const int32_t* __restrict__ live, int N,
+    int total, float r2, float inv_h, int max_nn, NormalsWs ws, float* __restrict__ normals,
+    int32_t* __restrict__ count, int32_t* __restrict__ flags) {
+  __shared__ uint64_t lists[MN_WAVES][MN_LIST];
+  const int b = blockIdx.y;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int q = blockIdx.x * MN_WAVES + wave;
+  if (q >= N) return;   // the whole wave
+  const int n_live = normals_live(live, b, N);
+  const float* __restrict__ p0 = cloud + (size_t)b * 3 * N;
+  float* __restrict__ o = normals + (size_t)b * 3 * N;
+  if (q >= n_live) {    // padding: neither a query nor a key
+    if (lane == 0) {
+      o[q] = 0.f; o[N + q] = 0.f; o[2 * (size_t)N + q] = 0.f;
+      count[(size_t)b * N + q] = 0;
+      flags[(size_t)b * N + q] = EN_PADDING;
+    }
+    return;
+  }
+  const float x = p0[q], y = p0[N + q], z = p0[2 * (size_t)N + q];
+  if (!(finite(x) && finite(y) && finite(z))) {   // no neighbourhood, no direction to turn to
+    if (lane == 0) {
+      o[q] = 0.f; o[N + q] = 0.f; o[2 * (size_t)N + q] = 1.f;
+      count[(size_t)b * N + q] = 0;
+      flags[(size_t)b * N + q] = EN_NONFINITE;
+    }
+    return;
+  }
+  MnSelect s;
+  s.list = lists[wave];
+  s.thr = ~0ull;
+  s.n = 0;
+  s.inside = 0;
+  s.max_nn = max_nn;
+  s.lane = lane;
+  const float4 org = ws.origin[b];
+  const bool grid = ws.m.flags[b] == 0 && grid_coord_ok(x, org.x, inv_h) && grid_coord_ok(y, org.y, inv_h) &&
+                    grid_coord_ok(z, org.z, inv_h);
+  if (grid) {
+    const int icx = grid_coord(x, org.x, inv_h), icy = grid_coord(y, org.y, inv_h), icz = grid_coord(z, org.z, inv_h);
+    const int* __restrict__ start = ws.m.start + (size_t)b * MN_CELLS;
+    // lane r < 9 fetches row r's runs, as match_query_kernel does
+    int vb0 = 0, ve0 = 0, vb1 = 0, ve1 = 0;
+    if (lane < 9) {
+      const int dz = lane / 3 - 1, dy = lane % 3 - 1;
+      const int row = mn_cell(0, icy + dy, icz + dz);
+      const int x0 = (icx - 1) & (MN_DIM - 1);
+      vb0 = start[row + x0];
+      if (x0 <= MN_DIM - 3) {
+        ve0 = start[row + x0 + 3];
+      } else {
+        ve0 = start[row + MN_DIM];
+        vb1 = start[row];
+        ve1 = start[row + ((x0 + 3) & (MN_DIM - 1))];
+      }
+    }
+    const float4* __restrict__ rec = ws.m.rec;   // the starts are offsets into the whole chunk
+    for (int r = 0; r < 9; ++r) {
+      for (int run = 0; run < 2; ++run) {
+        int rb = __shfl(run ? vb1 : vb0, r), re = __shfl(run ? ve1 : ve0, r);
+        rb = rb < 0 ? 0 : rb;
+        re = re > total ? total : re;
+        for (int base = rb; base < re; base += 64) {
+          const int i = base + lane;
+          const bool valid = i < re;
+          float4 c = make_float4(0.f, 0.f, 0.f, 0.f);
+          if (valid) c = rec[i];
+          s.consider(valid, dist2<false>(x, y, z, c.x, c.y, c.z), r2, __float_as_int(c.w));
+        }
+      }
+    }
+  } else {
+    for (int base = 0; base < n_live; base += 64) {   // a point that is not finite fails the comparison by itself
+      const int j = base + lane;
+      const bool valid = j < n_live;
+      float cx = 0.f, cy = 0.f, cz = 0.f;
+      if (valid) { cx = p0[j]; cy = p0[N + j]; cz = p0[2 * (size_t)N + j]; }
+      s.consider(valid, dist2<false>(x, y, z, cx, cy, cz), r2, j);
+    }
+  }
+  s.cut();   // ascending, at most max_nn
+  const int k = s.n < max_nn ? s.n : max_nn;
+  // the kept points, rank r in lane r: differences to the query in double, moments by the fixed butterfly
+  double dx = 0.0, dy = 0.0, dz = 0.0;
+  if (lane < k) {
+    const uint32_t j = (uint32_t)s.list[lane];
+    if (j < (uint32_t)N) {   // (cannot be otherwise: the index is the cloud's own)
+      dx = (double)p0[j] - (double)x;
+      dy = (double)p0[N + j] - (double)y;
+      dz = (double)p0[2 * (size_t)N + j] - (double)z;
+    }
+  }
+  const double s1x = mn_wave_sum(dx), s1y = mn_wave_sum(dy), s1z = mn_wave_sum(dz);
+  const double sxx = mn_wave_sum(dx * dx), syy = mn_wave_sum(dy * dy), szz = mn_wave_sum(dz * dz);
+  const double sxy = mn_wave_sum(dx * dy), sxz = mn_wave_sum(dx * dz), syz = mn_wave_sum(dy * dz);
+  int flag = s.inside > max_nn ? EN_CAPPED : 0;
+  double nx = 0.0, ny = 0.0, nz = 1.0;
+  if (k < EN_FEW) {
+    flag |= EN_FEWBIT;
+  } else if (sxx + syy + szz == 0.0) {   // every kept point is the query's copy (a square of a difference is 0 only there)
+    flag |= EN_DEGENERATE;
+  } else {
+    const double ik = 1.0 / (double)k;
+    const double mx = s1x * ik, my = s1y * ik, mz = s1z * ik;
+    double a00 = sxx * ik - mx * mx, a11 = syy * ik - my * my, a22 = szz * ik - mz * mz;
+    double a01 = sxy * ik - mx * my, a02 = sxz * ik - mx * mz, a12 = syz * ik - my * mz;
+    const double big = fmax(fmax(fmax(fabs(a00), fabs(a11)), fabs(a22)), fmax(fmax(fabs(a01), fabs(a02)), fabs(a12)));
+    bool solved = false;
+    if (big > 0.0 && finite(big)) {
+      const double sc = 1.0 / big;
+      a00 *= sc; a11 *= sc; a22 *= sc; a01 *= sc; a02 *= sc; a12 *= sc;
+      double v00 = 1.0, v01 = 0.0, v02 = 0.0, v10 = 0.0, v11 = 1.0, v12 = 0.0, v20 = 0.0, v21 = 0.0, v22 = 1.0;
+      for (int sw = 0; sw < EN_SWEEPS; ++sw) {
+        if (!(fabs(a01) + fabs(a02) + fabs(a12) > 1e-24)) break;
+        normals_rotate(a00, a11, a01, a02, a12, v00, v01, v10, v11, v20, v21);
+        normals_rotate(a00, a22, a02, a01, a12, v00, v02, v10, v12, v20, v22);
+        normals_rotate(a11, a22, a12, a01, a02, v01, v02, v11, v12, v21, v22);
+      }
+      // the smallest eigenvalue, the lowest column on a tie
+      double ex = v00, ey = v10, ez = v20, e = a00;
+      if (a11 < e) { ex = v01; ey = v11; ez = v21; e = a11; }
+      if (a22 < e) { ex = v02; ey = v12; ez = v22; e = a22; }
+      const double len = sqrt(ex * ex + ey * ey + ez * ez);
+      if (len > 0.0 && finite(len)) {
+        nx = ex / len; ny = ey / len; nz = ez / len;
+        solved = true;
+      }
+    }
+    if (!solved) flag |= EN_DEGENERATE;
+  }
+  // sign: towards the camera; without a direction the component of largest magnitude is positive, the lowest axis on a
+  // tie (the rule of s4g_darboux_frames_f32)
+  double dot = 0.0;
+  if (camera != nullptr) {
+    const float* __restrict__ c0 = camera + (size_t)b * 3;
+    const double rx = (double)c0[0] - (double)x, ry = (double)c0[1] - (double)y, rz = (double)c0[2] - (double)z;
+    if (finite(rx) && finite(ry) && finite(rz)) dot = nx * rx + ny * ry + nz * rz;
+  }
+  bool flip = dot < 0.0;
+  if (dot == 0.0) {
+    double lead = nx;
+    if (fabs(ny) > fabs(lead)) lead = ny;
+    if (fabs(nz) > fabs(lead)) lead = nz;
+    flip = lead < 0.0;
+  }
+  if (flip) { nx = -nx; ny = -ny; nz = -nz; }
+  if (lane != 0) return;
+  o[q] = (float)nx;
+  o[N + q] = (float)ny;
+  o[2 * (size_t)N + q] = (float)nz;
+  count[(size_t)b * N + q] = k;
+  flags[(size_t)b * N + q] = flag;
+}
+
+}  // namespace s4g
+
+extern "C" size_t s4g_estimate_normals_workspace_bytes(int64_t B, int64_t N) {
+  if (B <= 0 || N <= 0 || N >= (1ll << 30)) return 0;
+  return s4g::normals_ws(nullptr, s4g::normals_chunk(B, N), N, nullptr);
+}
+
+extern "C" int s4g_estimate_normals_f32(const float* cloud_b3n, const float* camera_b3, const int32_t* live_b, int64_t B,
+                                        int64_t N, float radius, int32_t max_nn, float* normals_b3n, int32_t* count_bn,
+                                        int32_t* flags_bn, void* workspace, size_t workspace_bytes,
+                                        s4g_stream_t stream) {
+  using namespace s4g;
+  if (B < 0 || B > 65535 || N < 0 || N >= (1ll << 30)) return S4G_EINVAL;
+  if (!(radius > 0.f) || !(radius < 1e18f) || max_nn < 1 || max_nn > MN_MAX_NN) return S4G_EINVAL;
+  if (B == 0 || N == 0) return S4G_OK;
+  if (!cloud_b3n || !normals_b3n || !count_bn || !flags_bn) return S4G_EINVAL;
+  hipStream_t st = (hipStream_t)stream;
+  const float r2 = radius * radius;                      // as match_run: the fp32 product,
+  const float h = radius * (1.0f + 1.0f / 256.0f);       // the cell edge slightly above the radius
+  const float inv_h = 1.0f / h;
+  const int64_t chunk = normals_chunk(B, N);
+  const size_t need = normals_ws(nullptr, chunk, N, nullptr);
+  if (!workspace || workspace_bytes < need) return S4G_EWORKSPACE;
+  for (int64_t b0 = 0; b0 < B; b0 += chunk) {
+    const int64_t Bc = B - b0 < chunk ? B - b0 : chunk;
+    NormalsWs w = {};
+    normals_ws(workspace, Bc, N, &w);
+    const size_t n = (size_t)Bc * (size_t)N, cells = (size_t)Bc * MN_CELLS + 1;
+    const float* xyz = cloud_b3n + (size_t)b0 * 3 * N;
+    const int32_t* lv = live_b ? live_b + b0 : nullptr;
+    const size_t n4 = mn_clear_int4(Bc);
+    hipLaunchKernelGGL(match_clear_kernel, dim3((unsigned)((n4 + MN_BUILD_THREADS - 1) / MN_BUILD_THREADS)),
+                       dim3(MN_BUILD_THREADS), 0, st, (int4*)w.m.count, n4);
+    S4G_LAUNCH_CHECK();
+    hipLaunchKernelGGL(normals_origin_kernel, dim3((unsigned)Bc), dim3(MN_BUILD_THREADS), 0, st, xyz, lv, (int)N,
+                       w.origin);
+    S4G_LAUNCH_CHECK();
+    const dim3 bgrid((unsigned)((N + MN_BUILD_THREADS - 1) / MN_BUILD_THREADS), (unsigned)Bc);
+    hipLaunchKernelGGL(normals_keys_kernel, bgrid, dim3(MN_BUILD_THREADS), 0, st, xyz, lv, (int)N, (int)Bc, inv_h, w);
+    S4G_LAUNCH_CHECK();
+    unsigned bits = MN_CELL_BITS;   // scene numbers 0 .. Bc: Bc itself marks the points no cell holds
+    while (bits < 32 && ((int64_t)1 << (bits - MN_CELL_BITS)) < Bc + 1) ++bits;
+    if (int rc = radix_sort_pairs(w.m.sort, radix_sort_ws_bytes(n), w.m.keys_a, w.m.keys_b, w.m.vals_a, w.m.vals_b, n,
+                                  bits, st))
+      return rc;
+    if (int rc = exclusive_scan_i32(w.m.scan, scan_ws_bytes(cells), w.m.count, w.m.start, cells, st)) return rc;
+    hipLaunchKernelGGL(normals_order_kernel, bgrid, dim3(MN_BUILD_THREADS), 0, st, xyz, (int)N, (int)Bc, w);
+    S4G_LAUNCH_CHECK();
+    const dim3 qgrid((unsigned)((N + MN_WAVES - 1) / MN_WAVES), (unsigned)Bc);
+    hipLaunchKernelGGL(normals_query_kernel, qgrid, dim3(MN_THREADS), 0, st, xyz,
+                       camera_b3 ? camera_b3 + (size_t)b0 * 3 : nullptr, lv, (int)N, (int)n, r2, inv_h, (int)max_nn, w,
+                       normals_b3n + (size_t)b0 * 3 * N, count_bn + (size_t)b0 * N, flags_bn + (size_t)b0 * N);
+    S4G_LAUNCH_CHECK();
+  }
+  return S4G_OK;
+}

@@ -895,20 +895,111 @@ def match_normals(cloud, scene_points, scene_normals, camera=None, radius=CURVAT
     return MatchedNormals(normals, count, flags, unbatched)
 
 
+NORMAL_RADIUS = 0.01                       # data_gen/configs/config.py: NORMAL_RADIUS
+
+
+@dataclass
+class EstimatedNormals:
+    """What `estimate_normals` returns: device tensors, one column per cloud point.  `normals` (B, 3, N) fp32, `count`
+    (B, N) int32 the number of kept neighbours (at most max_nn, the point itself among them), `flags` (B, N) int32 the
+    kernel's own (bit 0 = capped, bit 1 = few, bit 2 = degenerate, bit 3 = not finite, bit 4 = padding)."""
+    normals: torch.Tensor
+    count: torch.Tensor
+    flags: torch.Tensor
+    unbatched: bool = False
+
+    capped = property(lambda self: (self.flags & 1) != 0)
+    few = property(lambda self: (self.flags & 2) != 0)
+    degenerate = property(lambda self: (self.flags & 4) != 0)
+    nonfinite = property(lambda self: (self.flags & 8) != 0)
+    padding = property(lambda self: (self.flags & 16) != 0)
+
+
+def estimate_normals(cloud, camera=None, radius=NORMAL_RADIUS, max_nn=NORMAL_MAX_NN, count=None):
+    """The reference's normal estimation -- `PointCloud.estimate_normals` (data_gen/pcd_classes/pointcloud.py:48-60,
+    cloud_processor.py:44-52): open3d's `estimate_normals(KDTreeSearchParamHybrid(radius, max_nn))`,
+    `normalize_normals` and `orient_normals_towards_camera_location` -- for every point of every cloud in one sync-free,
+    graph-capturable call -> `EstimatedNormals`, whose `normals` are the input of `estimate_frames`, `label_view` and
+    `label_baseline_view` for a cloud that has none.
+
+    cloud (B, 3, N) fp32; camera (B, 3) or (3,) (one location for every cloud) the camera location, None: no camera;
+    count (B,) int32 on the device (optional): the rows of cloud b at or past count[b] (clamped to [0, N]) are padding.
+    One cloud may be passed unbatched -- (3, N) -- and gets a leading 1: the result is ALWAYS batched (`unbatched`
+    set, as `match_normals` does).  Per point: the live finite points with squared distance < radius^2 (fp32, strict),
+    of them the max_nn smallest by (fp32 squared distance, index), the point itself included; their covariance about
+    their mean in double; the unit eigenvector of its smallest eigenvalue, turned towards the camera (n . (camera - p)
+    >= 0), rounded to fp32 once.  Without a camera, where that product is exactly 0 and where the camera is not finite
+    the component of largest magnitude is positive, the lowest axis winning a tie (`estimate_frames`' rule).
+
+    Decisions.  (1) Fewer than 3 kept neighbours: (0, 0, 1), given its sign as above; `few`.  (2) All kept points
+    identical, or a solve that gives no direction: the same; `degenerate`.  Collinear neighbours get a unit vector
+    perpendicular to their line and no flag.  (3) A point that is not finite: (0, 0, 1) as it stands, count 0,
+    `nonfinite`; it is nobody's neighbour and does not slow its cloud down.  (4) More than max_nn points in the radius:
+    `capped`.  (5) Padding rows: zero, count 0, `padding`."""
+    if not isinstance(cloud, torch.Tensor) or cloud.device.type != "cuda":
+        raise RuntimeError("cloud must be a CUDA tensor (there is no CPU fallback)")
+    if not float(radius) > 0.0:
+        raise ValueError("radius must be positive, got %r" % (radius,))
+    if not 1 <= int(max_nn) <= 64:
+        raise ValueError("max_nn must be in [1, 64], got %r" % (max_nn,))
+    if camera is not None and (not isinstance(camera, torch.Tensor) or camera.device.type != "cuda"):
+        raise RuntimeError("camera must be a CUDA tensor (there is no CPU fallback)")
+    if count is not None and (not isinstance(count, torch.Tensor) or count.device.type != "cuda"):
+        raise RuntimeError("count must be a CUDA tensor (there is no CPU fallback)")
+    unbatched = cloud.dim() == 2
+    if unbatched:
+        cloud = cloud[None]
+    xyz = _F._f32c(cloud, "cloud")
+    if xyz.dim() != 3 or xyz.size(1) != 3:
+        raise RuntimeError("cloud must be (B, 3, N)")
+    B, _, N = xyz.shape
+    cam = None
+    if camera is not None:
+        cam = _F._f32c(camera, "camera")
+        if cam.dim() == 1 and cam.numel() == 3:
+            cam = cam.view(1, 3).expand(B, 3)
+        if tuple(cam.shape) != (B, 3):
+            raise RuntimeError("camera must be (B, 3) or (3,)")
+        cam = cam.contiguous()
+    live = None
+    if count is not None:
+        if count.dtype != torch.int32:
+            raise RuntimeError("count must be int32, got %s" % count.dtype)
+        if tuple(count.shape) != (B,):
+            raise RuntimeError("count must be (B,)")
+        live = count.contiguous()
+    if len({t.device for t in (xyz, cam, live) if t is not None}) != 1:
+        raise RuntimeError("cloud, camera and count must live on one device")
+    dev = xyz.device
+    normals = torch.empty((B, 3, N), dtype=torch.float32, device=dev)
+    cnt = torch.empty((B, N), dtype=torch.int32, device=dev)
+    flags = torch.empty((B, N), dtype=torch.int32, device=dev)
+    ws, nbytes = _workspace(_cabi.lib().s4g_estimate_normals_workspace_bytes(B, N), dev)
+    with torch.cuda.device(dev):
+        rc = _cabi.lib().s4g_estimate_normals_f32(xyz.data_ptr(), None if cam is None else cam.data_ptr(),
+                                                  None if live is None else live.data_ptr(), B, N, float(radius),
+                                                  int(max_nn), normals.data_ptr(), cnt.data_ptr(), flags.data_ptr(),
+                                                  ws.data_ptr(), nbytes, _F._stream())
+    _cabi.check(rc, "estimate_normals")
+    return EstimatedNormals(normals, cnt, flags, unbatched)
+
+
 @dataclass
 class ViewLabels:
     """What `label_view` returns: the `LocalSearch` of the view's frames, the `DarbouxFrames` they came from and
     `cloud_index` (B, F): the cloud indices of the valid frames in ascending order, then -1 (`search.count` of them);
-    `matched`: the `MatchedNormals` the frames were estimated on, None unless `match_normal` was asked for."""
+    `matched`: the `MatchedNormals` the frames were estimated on, None unless `match_normal` was asked for;
+    `estimated`: the `EstimatedNormals` they were estimated on, None unless `estimate_normal` was."""
     search: LocalSearch
     darboux: DarbouxFrames
     cloud_index: torch.Tensor
     matched: MatchedNormals = None
+    estimated = None                        # (a plain attribute, set by `label_view`: the constructor's fields stay four)
 
 
 def label_view(cloud, normals, scene_points, scene_normals, scene_labels, config=None, frame_index=None,
-               frame_count=None, radius=CURVATURE_RADIUS, min_neighbours=5, match_normal=False, camera=None,
-               max_nn=NORMAL_MAX_NN):
+               frame_count=None, radius=CURVATURE_RADIUS, min_neighbours=5, estimate_normal=False, match_normal=False,
+               camera=None, max_nn=NORMAL_MAX_NN):
     """`TorchSingleViewPointCloud.run_score(scene, match_normal)` (:182-201): view cloud in, S4G labels out, in one
     sync-free call -- `match_normals` where match_normal is set (:189-190), the sampled indices (:53, z >
     config.table_height + 0.015, unless frame_index is given), `estimate_frames`, then `grade_local_search` on its
@@ -917,9 +1008,17 @@ def label_view(cloud, normals, scene_points, scene_normals, scene_labels, config
     in the reference's eval mode).  One unbatched view (3, N) gets a leading 1, with its scene if that is unbatched
     too; the results are always batched.  match_normal=True: `normals` may be None; the view's normals are
     `match_normals(cloud, scene_points, scene_normals, camera, radius, max_nn).normals` (camera (B, 3) or (3,): the
-    camera location) and `ViewLabels.matched` holds that result."""
+    camera location) and `ViewLabels.matched` holds that result.  estimate_normal=True
+    (`TorchSingleViewPointCloud(estimate_normals=True)`, :58-59; exclusive with match_normal): `normals` may be None
+    as well; the view's normals are `estimate_normals(cloud, camera, radius, max_nn).normals` and
+    `ViewLabels.estimated` holds that result."""
     cfg = config or LocalSearchConfig()
-    matched = None
+    matched = estimated = None
+    if match_normal and estimate_normal:
+        raise ValueError("match_normal and estimate_normal exclude each other")
+    if estimate_normal:
+        estimated = estimate_normals(cloud, camera, radius, max_nn)
+        normals = estimated.normals[0] if estimated.unbatched else estimated.normals
     if match_normal:
         matched = match_normals(cloud, scene_points, scene_normals, camera, radius, max_nn)
         normals = matched.normals[0] if isinstance(cloud, torch.Tensor) and cloud.dim() == 2 else matched.normals
@@ -928,7 +1027,9 @@ def label_view(cloud, normals, scene_points, scene_normals, scene_labels, config
     if d.unbatched and scene_points.dim() == 2:          # one view against one unbatched scene; a (1, ...) scene passes as is
         scene_points, scene_normals, scene_labels = scene_points[None], scene_normals[None], scene_labels[None]
     s = grade_local_search(d.points, d.frames, scene_points, scene_normals, scene_labels, cfg, d.frame_count)
-    return ViewLabels(s, d, map_cloud_index(s.valid_index, d.frame_index), matched)
+    out = ViewLabels(s, d, map_cloud_index(s.valid_index, d.frame_index), matched)
+    out.estimated = estimated
+    return out
 
 
 CS_MAX_LIST = 4                            # the compiled maximum of each shift list (csrc/contact_search.hip)
@@ -1482,19 +1583,36 @@ class BaselineLabels:
 
 
 def label_baseline_view(points, frames, scene_points, scene_normals, cloud=None, normals=None, config=None,
-                        projection=None, frame_count=None, x_range=None, capacity=None):
+                        projection=None, frame_count=None, x_range=None, capacity=None, camera=None):
     """`run_score` of `TorchBaseLineSingleViewPointCloud` (torch_baseline_single_view_point_cloud.py:158-181,220-331) as
     one sync-free call -> `BaselineLabels`: `grade_local_search` with one label for every scene point (which removes
     the label gate, the only difference between the two searches), `best_placement`, then `close_regions` of `cloud` /
     `normals` (default: the scene itself, as in that class) in the best placement of every valid frame.  The
     reference's stop after `grasp_num` valid frames is the caller's slice of `best.valid_index`; no stale slots, as in
     `grade_local_search`.  `TorchPrecomputedBaselinePointCloud`'s crop and maps are x_range=(0, finger_length) with the
-    view as `cloud`; its lookup of precomputed scene scores stays out of scope."""
+    view as `cloud`; its lookup of precomputed scene scores stays out of scope.
+
+    camera (B, 3) or (3,), the camera location: a cloud without normals gets them from `estimate_normals(cloud,
+    camera)` with the reference's radius and max_nn, as that class does for a cloud that has none (:69-70): `cloud`
+    may then come with normals=None, and scene_normals=None with cloud=None estimates the scene's.  Without `camera`
+    nothing is estimated and cloud and normals go together, as before."""
     cfg = config or LocalSearchConfig()
     if not isinstance(scene_points, torch.Tensor) or scene_points.device.type != "cuda":
         raise RuntimeError("scene_points must be a CUDA tensor (there is no CPU fallback)")
-    if (cloud is None) != (normals is None):
-        raise RuntimeError("cloud and normals go together")
+    if camera is None:
+        if (cloud is None) != (normals is None):
+            raise RuntimeError("cloud and normals go together")
+    else:
+        if cloud is None and normals is not None:
+            raise RuntimeError("cloud and normals go together")
+        if scene_normals is None:
+            if cloud is not None:
+                raise RuntimeError("scene_normals=None estimates the normals of the scene as the cloud: pass cloud=None")
+            est = estimate_normals(scene_points, camera)
+            scene_normals = est.normals[0] if est.unbatched else est.normals
+        elif cloud is not None and normals is None:
+            est = estimate_normals(cloud, camera)
+            normals = est.normals[0] if est.unbatched else est.normals
     lab_shape = scene_points.shape[:-2] + scene_points.shape[-1:]
     labels = torch.zeros(lab_shape, dtype=torch.int32, device=scene_points.device)
     search = grade_local_search(points, frames, scene_points, scene_normals, labels, cfg, frame_count)

@@ -137,6 +137,18 @@ class CloudPreProcessor:
     def remove_outliers(self, nb_points=NUM_POINTS_THRESHOLD, radius=RADIUS_THRESHOLD):
         self.points = self.points[:, radius_outlier_mask(self.points, nb_points, radius)].contiguous()
 
+    def estimate_normals(self, camera_pos=None):
+        """`CloudPreProcessor.estimate_normals(camera_pos=np.zeros(3))` (cloud_processor.py:44-52): the normals of
+        `points` by `postprocess.estimate_normals` with the reference's radius and max_nn, turned towards camera_pos
+        (default: the origin), stored in `normals` (3, N)."""
+        from .postprocess import estimate_normals as _estimate
+        if camera_pos is None:
+            cam = torch.zeros(3, dtype=torch.float32, device=self.points.device)
+        else:
+            cam = torch.as_tensor(camera_pos, dtype=torch.float32).reshape(3).to(self.points.device)
+        self.normals = _estimate(self.points, cam).normals[0]
+        return self.normals
+
 
 def sample_single_cloud(points, num_input=25600, seed=0, mode="random"):
     """(3, N) -> (3, num_input).  mode "random": seeded permutation / repetition;
