@@ -75,7 +75,10 @@ extern "C" {
  *     baseline's classifier on the packed close-region point sets, or on dense (G, 3, n) sets: two per-point trunks
  *     with a segment maximum and the per-set layers on the matrix cores); s4g_estimate_normals_f32 /
  *     s4g_estimate_normals_workspace_bytes (PCA normals of a cloud that has none: the input of all of the above for a
- *     sensor cloud). */
+ *     sensor cloud); s4g_contact_pairs_f32 / s4g_contact_pairs_workspace_bytes (the antipodal point pairs of an
+ *     object cloud) and s4g_contact_pair_grade_f32 / s4g_contact_pair_grade_workspace_bytes (their rolled frames
+ *     graded over that cloud, the kept frames and the object point of each: the per-object data the contact model's
+ *     scenes are composed from). */
 #define S4G_ABI_VERSION 14
 
 /* ---------------------------------------------------------------------------
@@ -1122,6 +1125,78 @@ int s4g_contact_select_f32(const int32_t *nearest_bn, const float *cloud_b3n, co
                            const int32_t *valid_bf, const float *search_bf, const float *antipodal_bf, int64_t B,
                            int64_t N, int64_t M, int64_t F, float *normals_b3n, int32_t *best_frame_bn,
                            float *point_score_bn, int32_t *valid_index_bn, int64_t *count_b, s4g_stream_t stream);
+
+/* The contact model's per-object frames (csrc/contact_pairs.hip): GenerateContactObjectData of
+ * data_gen/data_generator/data_object_contact_point_generator.py for every object of a batch, without host
+ * synchronisation.  Both entry points are run-to-run bit-identical and batch invariant: integer atomics and ballots
+ * only, no floating-point atomics.
+ *
+ * s4g_contact_pairs_f32 = cache_contact_pair (:103-123).  xyz, normals (B, 3, N) fp32, the normals of unit length;
+ * count_b (device, may be NULL): only the first count_b[b] points of object b are points.  Per i < j, in double from the
+ * fp32 inputs and in the reference's operation order:
+ *   d = |p_j - p_i|;  u = (p_j - p_i) / clip(d, 1e-4, 1);  c_ij = u . n_i;  c_ji = -u . n_j;  score = |c_ij * c_ji|;
+ *   the pair is kept when d < max_distance (2 * HALF_BOTTOM_SPACE) and score > cos_threshold (0.95), both strict, both
+ *   thresholds formed by the caller in double.  A point that is not finite, or at or past count_b[b], pairs with nothing.
+ * Outputs: pairs_bp2 int32 (B, max_pairs, 2) in the order of np.nonzero(np.triu(...)): ascending i, then ascending j;
+ *   pair_score_bp fp32 (B, max_pairs), the double rounded once; rows past the count are -1 / 0;
+ *   pair_count_b int64 (B): the exact count, also when the list does not fit; flags_b int32 (B): bit 0 = more than
+ *   max_pairs pairs (the first max_pairs are written, nothing past the end).
+ * Two passes over the same predicate (count per row, the library's scan, write by ballot rank): the order does not
+ * depend on arrival.  Cost: N * (N - 1) / 2 tests in double per object.
+ * Limits: 1 <= N <= 2^20, B * N * (N - 1) / 2 < 2^31 (the scan is int32), max_pairs < 2^24, B <= 65 535 (S4G_EINVAL).
+ * Workspace: s4g_contact_pairs_workspace_bytes(B, N); contents need not be initialised.
+ *
+ * s4g_contact_pair_grade_f32 = _estimate_grasp_quality with check_collision (:125-221) and get_frame_neighbor
+ * (:79-86) over pairs_bp2 (B, P, 2), of which the first pair_count_b[b] (device, may be NULL: all P) are graded.
+ * T rolls (theta_search, at most 16), W shifts (width_shift, at most 4).
+ *   params5 (HOST) = {HALF_BOTTOM_WIDTH, HALF_BOTTOM_SPACE, BACK_COLLISION_MARGIN, BOTTOM_LENGTH, FINGER_LENGTH}, each
+ *     formed in double and rounded to fp32 once;  gates3 (HOST, double) = {min_points, back_threshold, finger_threshold};
+ *   tables_12t2w (DEVICE, 12 T + 2 W floats) = rows 0..2 of torch.inverse(local_search_to_local)[theta] (:29-40), then
+ *     -HALF_HAND_THICKNESS + dw [W], HALF_HAND_THICKNESS + dw [W] rounded once.
+ * Per pair, once, in double and rounded to fp32 once: y = (p_j - p_i) / |.|, x = e_y - (e_y . y) y normalised,
+ * z = x cross y, c the midpoint, T = [R^T | -R^T c] (:139-152).  Per object point local = T p in fp32 as
+ * s4g_eval_frames_f32 forms it; a point with |ly| >= HBW contributes nothing; close_plane = |ly| < HBS, finger plane =
+ * HBS < |ly| < HBW; per roll s = L2LS[theta] local in fp32 in the same operation order; per roll and shift, with every
+ * inequality strict: back = count(sx < margin & sx > -BOTTOM_LENGTH & z), finger = count(sx > margin & sx <
+ * FINGER_LENGTH & z & finger plane), close = the same in the close plane, z = sz < HHT + dw & sz > -HHT + dw.
+ * Gates, in the reference's order: a pair with close_plane < min_points has no frame.  Per roll, shifts in the given
+ * order: skip one with back > back_threshold, then one with finger > finger_threshold, then one with close <
+ * min_points, else acc += close / 3 (an fp32 division, an fp32 add).  `last` is the LAST shift's value (:194-214): 0
+ * where that shift was skipped by a collision, its close count where it failed min_points alone.  The frame is valid
+ * when acc >= min_points and last >= min_points; its score is min(acc, last), an exact fp32 function of integers.
+ * Decisions.  (1) The frame is formed in double and its rigid inverse analytically, not by torch.inverse in fp32.
+ *   (2) A pair whose frame is not finite (y parallel to e_y, coincident points, a point that is not finite) gets no
+ *   frame and fail bit 0; the reference would propagate NaN.  (3) pair_score and antipodal_score are fp32, the double
+ *   rounded once; the reference keeps float64.  (4) Thresholds and search lists are configuration with the reference's
+ *   values as defaults, bounded by the small maxima above.
+ * Dense outputs: counts_bptw3 int32 (B, P, T, W, 3) = {back, finger, close}, counted whatever the gates say;
+ *   close_plane_bp int32 (B, P); score_bpt fp32, valid_bpt int32 (B, P, T); fail_bp int32 (B, P): bit 0 = the frame is
+ *   not finite, bit 1 = close_plane < min_points, bit 2 = an index outside the object.  Rows at or past
+ *   pair_count_b[b] read 0 everywhere.
+ * Frames out (max_frames rows per object): the valid (pair, roll) in ascending pair * T + roll, the reference's append
+ *   order: g2l_bf44 fp32 = L2LS[theta] @ T (:218); search_score_bf; antipodal_score_bf = pair_score_bp of the pair (0
+ *   where that is NULL); frame_source_bf int32 = pair * T + roll; frame_point_index_bf int32: the object point nearest
+ *   to the frame's centre, the translation of the rigid inverse of g2l, by fp32 squared distance in global coordinates
+ *   (the arithmetic of s4g_match_nearest_f32, no radius), the lower index winning a tie.  Rows past the count are 0 /
+ *   -1.  frame_count_b int64 (B): the exact count; flags_b int32 (B): bit 1 = more than max_frames frames.
+ * Cost: every object point is transformed for every pair, N * P * 18 flops; a point inside the gripper's width then
+ *   costs 14 flops per roll.  Limits: 1 <= N <= 2^20, P < 2^24, P * T < 2^30, max_frames < 2^30, B <= 65 535.
+ * Workspace: s4g_contact_pair_grade_workspace_bytes(B, N, P, T, W); contents need not be initialised; every launch of
+ * the call is a kernel. */
+size_t s4g_contact_pairs_workspace_bytes(int64_t B, int64_t N);
+int s4g_contact_pairs_f32(const float *xyz_b3n, const float *normals_b3n, const int64_t *count_b, int64_t B, int64_t N,
+                          int64_t max_pairs, double max_distance, double cos_threshold, int32_t *pairs_bp2,
+                          float *pair_score_bp, int64_t *pair_count_b, int32_t *flags_b, void *workspace,
+                          size_t workspace_bytes, s4g_stream_t stream);
+size_t s4g_contact_pair_grade_workspace_bytes(int64_t B, int64_t N, int64_t P, int64_t T, int64_t W);
+int s4g_contact_pair_grade_f32(const float *xyz_b3n, const int64_t *count_b, const int32_t *pairs_bp2,
+                               const float *pair_score_bp, const int64_t *pair_count_b, int64_t B, int64_t N, int64_t P,
+                               int64_t T, int64_t W, const float *params5, const double *gates3,
+                               const float *tables_12t2w, int64_t max_frames, int32_t *counts_bptw3,
+                               int32_t *close_plane_bp, float *score_bpt, int32_t *valid_bpt, int32_t *fail_bp,
+                               float *g2l_bf44, float *search_score_bf, float *antipodal_score_bf,
+                               int32_t *frame_source_bf, int32_t *frame_point_index_bf, int64_t *frame_count_b,
+                               int32_t *flags_b, void *workspace, size_t workspace_bytes, s4g_stream_t stream);
 
 /* ---- next row f3: cloud pre-processing on device -------------------------
  * Single-scene passes in front of the network (reference

@@ -68,6 +68,33 @@ def label_contact_view(*args, **kwargs):
     return _label(*args, **kwargs)
 
 
+def contact_pairs(*args, **kwargs):
+    """The antipodal point pairs of every object cloud of a batch in one call.  See `postprocess.contact_pairs`."""
+    from .postprocess import contact_pairs as _pairs
+    return _pairs(*args, **kwargs)
+
+
+def grade_contact_pairs(*args, **kwargs):
+    """The rolled frames of every pair graded over its object, the kept frames and the object point of each.  See
+    `postprocess.grade_contact_pairs`."""
+    from .postprocess import grade_contact_pairs as _grade
+    return _grade(*args, **kwargs)
+
+
+def label_contact_object(*args, **kwargs):
+    """Object cloud in, the contact model's per-object frames out: `contact_pairs` and `grade_contact_pairs` in one
+    call.  See `postprocess.label_contact_object`."""
+    from .postprocess import label_contact_object as _label
+    return _label(*args, **kwargs)
+
+
+def compose_contact_scene(*args, **kwargs):
+    """The per-object frames of posed objects as one scene for `grade_contact_frames` / `label_contact_view`.  See
+    `postprocess.compose_contact_scene`."""
+    from .postprocess import compose_contact_scene as _compose
+    return _compose(*args, **kwargs)
+
+
 def best_placement(*args, **kwargs):
     """The baseline data generator's best placement per frame of a `LocalSearch`.  See `postprocess.best_placement`."""
     from .postprocess import best_placement as _best

@@ -1376,6 +1376,341 @@ def label_contact_view(reference_cloud, cloud, scene_points, scene_normals, came
     return ContactLabels(nearest, normals, best, score, valid_index, count, search, xyz, ss, aps, unbatched)
 
 
+CP_MAX_THETA, CP_MAX_SHIFT = 16, 4         # the compiled maxima of csrc/contact_pairs.hip
+CP_FAIL_NONFINITE, CP_FAIL_PLANE, CP_FAIL_INDEX = 1, 2, 4
+CP_FLAG_PAIRS, CP_FLAG_FRAMES = 1, 2
+CP_DEFAULT_PAIRS_PER_POINT = 16            # the default capacities: max_pairs = min(N (N - 1) / 2, 16 N),
+CP_DEFAULT_FRAMES_PER_PAIR = 6             # max_frames = min(T, 6) max_pairs (the reference's camera: 6.7 and 3.6)
+
+
+@dataclass
+class ContactPairConfig:
+    """The constants of the contact model's per-object data (data_gen/data_generator/
+    data_object_contact_point_generator.py:15-18,193,173,209 and data_gen/configs/config.py:38-56): the gripper constants
+    of `ContactSearchConfig`, GASKET_RADIUS, COS_THR, THETA_SEARCH in degrees, the shifts of the hand along its
+    thickness in the reference's loop order, and the gates."""
+    back_collision_margin: float = 0.0
+    half_bottom_width: float = 0.057
+    bottom_length: float = 0.08
+    finger_width: float = 0.023
+    half_hand_thickness: float = 0.012
+    finger_length: float = 0.09
+    gasket_radius: float = 0.012
+    cos_threshold: float = 0.95
+    theta_search: tuple = tuple(range(0, 360, 30))
+    width_shift: tuple = (-0.015, 0.015, 0)
+    min_points: float = 50
+    back_threshold: float = 0
+    finger_threshold: float = 0
+
+    @property
+    def half_bottom_space(self):
+        return self.half_bottom_width - self.finger_width
+
+    @property
+    def max_distance(self):
+        return self.half_bottom_space * 2                       # :105, in Python floats
+
+    def check(self):
+        if not 1 <= len(self.theta_search) <= CP_MAX_THETA:
+            raise ValueError("theta_search needs 1..%d entries, got %d" % (CP_MAX_THETA, len(self.theta_search)))
+        if not 1 <= len(self.width_shift) <= CP_MAX_SHIFT:
+            raise ValueError("width_shift needs 1..%d entries, got %d" % (CP_MAX_SHIFT, len(self.width_shift)))
+
+    def local_to_local_search(self):
+        """`torch.inverse(local_search_to_local)` built as the reference builds it (:29-40): float64 numpy rolls about
+        y composed with the move-back of FINGER_LENGTH - GASKET_RADIUS, rounded to fp32, inverted in fp32 on the CPU
+        -> (T, 4, 4) fp32 CPU tensor."""
+        import numpy as np
+        self.check()
+        T = len(self.theta_search)
+        back = np.eye(4)
+        back[0, 3] = -(self.finger_length - self.gasket_radius)
+        m = np.tile(np.eye(4), (T, 1, 1))
+        for i, th in enumerate(self.theta_search):
+            m[i, 0, 0] = np.cos(th / 180 * np.pi)
+            m[i, 2, 2] = np.cos(th / 180 * np.pi)
+            m[i, 0, 2] = np.sin(th / 180 * np.pi)
+            m[i, 2, 0] = -np.sin(th / 180 * np.pi)
+        return torch.inverse(torch.tensor(m @ back, dtype=torch.float))
+
+    def tables(self):
+        """The device table of `s4g_contact_pair_grade_f32`: rows 0..2 of every roll's matrix, then the lower and the
+        upper z bound of every shift, each formed in Python floats and rounded to fp32 once -> (12 T + 2 W,) fp32."""
+        hht = self.half_hand_thickness
+        z = torch.tensor([-hht + float(d) for d in self.width_shift] + [hht + float(d) for d in self.width_shift],
+                         dtype=torch.float64).to(torch.float32)
+        return torch.cat([self.local_to_local_search()[:, :3, :].reshape(-1), z])
+
+
+@dataclass
+class ContactPairs:
+    """What `contact_pairs` returns: `pairs` (B, max_pairs, 2) int32 in ascending (i, j) then -1, `score` (B, max_pairs)
+    fp32, `count` (B,) int64 the exact number of pairs, `flags` (B,) int32 (`CP_FLAG_PAIRS`: the list did not fit)."""
+    pairs: torch.Tensor
+    score: torch.Tensor
+    count: torch.Tensor
+    flags: torch.Tensor
+    config: ContactPairConfig
+    unbatched: bool = False
+
+
+@dataclass
+class ContactPairGrades:
+    """What `grade_contact_pairs` returns.  Dense, one row per pair: `counts` (B, P, T, W, 3) int32 = {back, finger,
+    close}, `close_plane` (B, P) int32, `score` (B, P, T) fp32, `valid_i32` (B, P, T), `fail` (B, P) int32
+    (`CP_FAIL_*`).  The kept frames, `max_frames` rows per object in ascending pair * T + roll: `global_to_local`
+    (B, F, 4, 4) fp32, `search_score`, `antipodal_score` (B, F) fp32, `frame_source` (B, F) int32 = pair * T + roll,
+    `frame_point_index` (B, F) int32, `frame_count` (B,) int64 the exact number, `flags` (B,) int32
+    (`CP_FLAG_FRAMES`: the list did not fit)."""
+    counts: torch.Tensor
+    close_plane: torch.Tensor
+    score: torch.Tensor
+    valid_i32: torch.Tensor
+    fail: torch.Tensor
+    global_to_local: torch.Tensor
+    search_score: torch.Tensor
+    antipodal_score: torch.Tensor
+    frame_source: torch.Tensor
+    frame_point_index: torch.Tensor
+    frame_count: torch.Tensor
+    flags: torch.Tensor
+    config: ContactPairConfig
+    unbatched: bool = False
+
+    valid = property(lambda self: self.valid_i32 != 0)
+
+
+def _object_cloud(points, normals, count):
+    """points (and normals) (B, 3, N) fp32 on one device, N >= 1; an unbatched cloud gets a leading 1."""
+    named = [("points", points)] + ([] if normals is None else [("normals", normals)])
+    for name, t in named:
+        if not isinstance(t, torch.Tensor) or t.device.type != "cuda":
+            raise RuntimeError("%s must be a CUDA tensor (there is no CPU fallback)" % name)
+    unbatched = points.dim() == 2
+    if unbatched:
+        points = points[None]
+        normals = None if normals is None else normals[None]
+        if isinstance(count, torch.Tensor) and count.dim() == 0:
+            count = count[None]
+    xyz = _F._f32c(points, "points")
+    if xyz.dim() != 3 or xyz.size(1) != 3 or xyz.size(2) < 1:
+        raise RuntimeError("points must be (B, 3, N) with N >= 1")
+    nrm = None
+    if normals is not None:
+        nrm = _F._f32c(normals, "normals")
+        if tuple(nrm.shape) != tuple(xyz.shape) or nrm.device != xyz.device:
+            raise RuntimeError("normals must be (B, 3, N) like points, on the same device")
+    cnt = _scene_count(count, xyz.size(0), xyz.device, "count")
+    return xyz, nrm, cnt, unbatched
+
+
+def contact_pairs(points, normals, config=None, count=None, max_pairs=None):
+    """`GenerateContactObjectData.cache_contact_pair` (data_object_contact_point_generator.py:103-123) for every object
+    of a batch in one sync-free, graph-capturable call -> `ContactPairs`.  points, normals (B, 3, N) fp32, the normals
+    of unit length; count (B,) on the device (optional): the points of object b are its first count[b].  The test runs
+    in double from the fp32 inputs; the list comes in the order of `np.nonzero(np.triu(...))`.  max_pairs: the rows of
+    the padded list (default min(N (N - 1) / 2, 16 N)); `count` stays exact and `flags` says when it did not fit."""
+    cfg = config or ContactPairConfig()
+    cfg.check()
+    xyz, nrm, cnt, unbatched = _object_cloud(points, normals, count)
+    B, _, N = xyz.shape
+    dev = xyz.device
+    if max_pairs is None:
+        max_pairs = min(N * (N - 1) // 2, CP_DEFAULT_PAIRS_PER_POINT * N)
+    max_pairs = int(max_pairs)
+    pairs = torch.empty((B, max_pairs, 2), dtype=torch.int32, device=dev)
+    score = torch.empty((B, max_pairs), dtype=torch.float32, device=dev)
+    pcount = torch.empty((B,), dtype=torch.int64, device=dev)
+    flags = torch.empty((B,), dtype=torch.int32, device=dev)
+    ws, nbytes = _workspace(_cabi.lib().s4g_contact_pairs_workspace_bytes(B, N), dev)
+    with torch.cuda.device(dev):
+        rc = _cabi.lib().s4g_contact_pairs_f32(xyz.data_ptr(), nrm.data_ptr(), None if cnt is None else cnt.data_ptr(),
+                                               B, N, max_pairs, float(cfg.max_distance), float(cfg.cos_threshold),
+                                               pairs.data_ptr(), score.data_ptr(), pcount.data_ptr(), flags.data_ptr(),
+                                               ws.data_ptr(), nbytes, _F._stream())
+    _cabi.check(rc, "contact_pairs")
+    return ContactPairs(pairs, score, pcount, flags, cfg, unbatched)
+
+
+def grade_contact_pairs(points, pairs, config=None, count=None, pair_count=None, pair_score=None, max_frames=None):
+    """`_estimate_grasp_quality` with `check_collision` and `get_frame_neighbor` (data_object_contact_point_generator.py:
+    79-86,125-221) for every pair of every object in one sync-free, graph-capturable call -> `ContactPairGrades`.
+    points (B, 3, N) fp32; pairs (B, P, 2) int32 or a `ContactPairs` (its count and score are then the defaults);
+    pair_count (B,) on the device (optional): the pairs of object b are its first pair_count[b]; pair_score (B, P) fp32
+    (optional) becomes `antipodal_score`.  max_frames: the rows of the frame list (default min(T, 6) P).
+
+    Four decisions.  (1) The frame of a pair is formed in double and its rigid inverse analytically, not by
+    `torch.inverse` in fp32.  (2) A pair whose frame is not finite gets no frame and `CP_FAIL_NONFINITE`; the reference
+    would propagate NaN.  (3) `antipodal_score` is fp32; the reference keeps float64.  (4) Thresholds and search lists
+    are configuration, at most 16 rolls and 4 shifts."""
+    cfg = config or (pairs.config if isinstance(pairs, ContactPairs) else ContactPairConfig())
+    cfg.check()
+    if isinstance(pairs, ContactPairs):
+        pair_count = pairs.count if pair_count is None else pair_count
+        pair_score = pairs.score if pair_score is None else pair_score
+        pairs = pairs.pairs
+    xyz, _, cnt, unbatched = _object_cloud(points, None, count)
+    B, _, N = xyz.shape
+    dev = xyz.device
+    if not isinstance(pairs, torch.Tensor) or pairs.device != dev or pairs.dtype != torch.int32:
+        raise RuntimeError("pairs must be an int32 tensor on the device of points")
+    if pairs.dim() == 2:
+        pairs = pairs[None]
+        pair_score = pair_score[None] if pair_score is not None and pair_score.dim() == 1 else pair_score
+    if pairs.dim() != 3 or pairs.size(0) != B or pairs.size(2) != 2:
+        raise RuntimeError("pairs must be (B, P, 2)")
+    pairs = pairs.contiguous()
+    P = pairs.size(1)
+    if pair_score is not None:
+        pair_score = _F._f32c(pair_score, "pair_score")
+        if tuple(pair_score.shape) != (B, P) or pair_score.device != dev:
+            raise RuntimeError("pair_score must be (B, P) on the device of points")
+    pcnt = _scene_count(pair_count, B, dev, "pair_count")
+    T, W = len(cfg.theta_search), len(cfg.width_shift)
+    if max_frames is None:
+        max_frames = min(T, CP_DEFAULT_FRAMES_PER_PAIR) * P
+    F = int(max_frames)
+    tables = _small_on_device(cfg.tables(), torch.float32, dev)
+    i32 = lambda *shape: torch.empty(shape, dtype=torch.int32, device=dev)            # noqa: E731
+    f32 = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)          # noqa: E731
+    out = ContactPairGrades(i32(B, P, T, W, 3), i32(B, P), f32(B, P, T), i32(B, P, T), i32(B, P), f32(B, F, 4, 4),
+                            f32(B, F), f32(B, F), i32(B, F), i32(B, F),
+                            torch.empty((B,), dtype=torch.int64, device=dev), i32(B), cfg, unbatched)
+    once = lambda v: float(torch.tensor(v, dtype=torch.float64).to(torch.float32))    # noqa: E731  (one rounding)
+    params = (ctypes.c_float * 5)(once(cfg.half_bottom_width), once(cfg.half_bottom_space),
+                                  once(cfg.back_collision_margin), once(cfg.bottom_length), once(cfg.finger_length))
+    gates = (ctypes.c_double * 3)(float(cfg.min_points), float(cfg.back_threshold), float(cfg.finger_threshold))
+    ws, nbytes = _workspace(_cabi.lib().s4g_contact_pair_grade_workspace_bytes(B, N, P, T, W), dev)
+    ptr = lambda t: None if t is None or t.numel() == 0 else t.data_ptr()             # noqa: E731
+    with torch.cuda.device(dev):
+        rc = _cabi.lib().s4g_contact_pair_grade_f32(
+            xyz.data_ptr(), ptr(cnt), ptr(pairs), ptr(pair_score), ptr(pcnt), B, N, P, T, W, params, gates,
+            tables.data_ptr(), F, ptr(out.counts), ptr(out.close_plane), ptr(out.score), ptr(out.valid_i32),
+            ptr(out.fail), ptr(out.global_to_local), ptr(out.search_score), ptr(out.antipodal_score),
+            ptr(out.frame_source), ptr(out.frame_point_index), out.frame_count.data_ptr(), out.flags.data_ptr(),
+            ws.data_ptr(), nbytes, _F._stream())
+    _cabi.check(rc, "contact_pair_grade")
+    return out
+
+
+@dataclass
+class ObjectContactFrames:
+    """What `label_contact_object` returns: the kept frames of every object -- `global_to_local` (B, F, 4, 4),
+    `search_score`, `antipodal_score` (B, F) fp32, `frame_point_index` (B, F) int32, `frame_count` (B,) int64 -- with
+    the `pairs` (`ContactPairs`) and `grades` (`ContactPairGrades`) behind them, `flags` (B,) int32 the union of
+    theirs, and the cloud as given."""
+    global_to_local: torch.Tensor
+    search_score: torch.Tensor
+    antipodal_score: torch.Tensor
+    frame_point_index: torch.Tensor
+    frame_count: torch.Tensor
+    flags: torch.Tensor
+    pairs: ContactPairs
+    grades: ContactPairGrades
+    points: torch.Tensor
+    normals: torch.Tensor
+    count: torch.Tensor
+    unbatched: bool = False
+
+    def dump(self, b=0):
+        """The dictionary the reference pickles per object (:65-74) for object b, as numpy.  Reads the counts on the
+        host."""
+        n = self.points.shape[2] if self.count is None else int(self.count[b])
+        f = min(int(self.frame_count[b]), self.global_to_local.shape[1])
+        return {"cloud": self.points[b, :, :n].t().cpu().numpy(),
+                "normal": self.normals[b, :, :n].t().cpu().numpy(),
+                "global_to_local": self.global_to_local[b, :f].cpu().numpy(),
+                "search_score": self.search_score[b, :f].cpu().numpy(),
+                "antipodal_score": self.antipodal_score[b, :f].cpu().numpy(),
+                "frame_point_index": self.frame_point_index[b, :f].cpu().numpy()}
+
+
+def label_contact_object(points, normals, config=None, count=None, max_pairs=None, max_frames=None):
+    """`GenerateContactObjectData.run_loop` from the sampled cloud on (data_object_contact_point_generator.py:65-74):
+    object cloud in, the contact model's per-object frames out, in one sync-free, graph-capturable call on the
+    library's stream -> `ObjectContactFrames`.  `contact_pairs` then `grade_contact_pairs`; see both for the
+    arguments, the capacities and the four decisions."""
+    cfg = config or ContactPairConfig()
+    prs = contact_pairs(points, normals, cfg, count, max_pairs)
+    xyz, nrm, cnt, unbatched = _object_cloud(points, normals, count)
+    g = grade_contact_pairs(xyz, prs, cfg, cnt, max_frames=max_frames)
+    return ObjectContactFrames(g.global_to_local, g.search_score, g.antipodal_score, g.frame_point_index,
+                               g.frame_count, prs.flags | g.flags, prs, g, xyz, nrm, cnt, unbatched)
+
+
+def quaternion_matrix(q):
+    """A (w, x, y, z) quaternion -> the 3 x 3 rotation, as `transforms3d.quaternions.quat2mat` forms it (float64; a
+    quaternion shorter than the float epsilon gives the identity)."""
+    w, x, y, z = (float(v) for v in q)
+    nq = w * w + x * x + y * y + z * z
+    if nq < 2.220446049250313e-16:
+        return torch.eye(3, dtype=torch.float64)
+    s = 2.0 / nq
+    X, Y, Z = x * s, y * s, z * s
+    wX, wY, wZ, xX, xY, xZ, yY, yZ, zZ = w * X, w * Y, w * Z, x * X, x * Y, x * Z, y * Y, y * Z, z * Z
+    return torch.tensor([[1.0 - (yY + zZ), xY - wZ, xZ + wY],
+                         [xY + wZ, 1.0 - (xX + zZ), yZ - wX],
+                         [xZ - wY, yZ + wX, 1.0 - (xX + yY)]], dtype=torch.float64)
+
+
+def pose_matrix(pose):
+    """A pose as the scene generator keeps it -- (x, y, z, qw, qx, qy, qz) -> 4 x 4 float64 (:58-62)."""
+    t = torch.as_tensor(pose, dtype=torch.float64)
+    if tuple(t.shape) != (7,):
+        raise ValueError("a pose is (x, y, z, qw, qx, qy, qz)")
+    m = torch.eye(4, dtype=torch.float64)
+    m[:3, :3] = quaternion_matrix(t[3:].tolist())
+    m[:3, 3] = t[:3].cpu()
+    return m
+
+
+@dataclass
+class ContactScene:
+    """What `compose_contact_scene` returns, one scene: `points`, `normals` (3, M) fp32, `labels` (M,) int32,
+    `global_to_local` (F, 4, 4) fp32, `search_score`, `antipodal_score` (F,) fp32, `frame_point_index` (F,) int32 into
+    the scene's points."""
+    points: torch.Tensor
+    normals: torch.Tensor
+    labels: torch.Tensor
+    global_to_local: torch.Tensor
+    search_score: torch.Tensor
+    antipodal_score: torch.Tensor
+    frame_point_index: torch.Tensor
+
+
+def compose_contact_scene(objects, poses, labels=None):
+    """`GenerateContactScene.generate_single_scene` (data_gen/data_generator/data_contact_scene_generator.py:57-100) in
+    torch on the device: objects, a list of (`ObjectContactFrames`, b) or of unbatched `ObjectContactFrames`; poses,
+    one (x, y, z, qw, qx, qy, qz) each; labels, one int each (default 0, 1, ...).  Points and normals
+    are moved by the pose, global_to_local becomes global_to_local @ inverse(pose), frame_point_index is offset by the
+    running point count, everything is concatenated -> `ContactScene`, which goes straight into
+    `grade_contact_frames` / `label_contact_view`.  Reads every object's counts on the host."""
+    if len(objects) != len(poses) or not objects:
+        raise ValueError("one pose per object, at least one object")
+    parts = {k: [] for k in ("points", "normals", "labels", "g2l", "search", "antipodal", "index")}
+    offset = 0
+    for k, (obj, pose) in enumerate(zip(objects, poses)):
+        obj, b = obj if isinstance(obj, tuple) else (obj, 0)
+        dev = obj.points.device
+        n = obj.points.shape[2] if obj.count is None else int(obj.count[b])
+        f = min(int(obj.frame_count[b]), obj.global_to_local.shape[1])
+        m = pose_matrix(pose)
+        m32 = m.to(torch.float32).to(dev)
+        inv32 = torch.linalg.inv(m).to(torch.float32).to(dev)
+        parts["points"].append(m32[:3, :3] @ obj.points[b, :, :n] + m32[:3, 3:])
+        parts["normals"].append(m32[:3, :3] @ obj.normals[b, :, :n])
+        parts["labels"].append(torch.full((n,), k if labels is None else int(labels[k]), dtype=torch.int32, device=dev))
+        parts["g2l"].append(obj.global_to_local[b, :f] @ inv32)
+        parts["search"].append(obj.search_score[b, :f])
+        parts["antipodal"].append(obj.antipodal_score[b, :f])
+        parts["index"].append(obj.frame_point_index[b, :f] + offset)
+        offset += n
+    return ContactScene(torch.cat(parts["points"], 1).contiguous(), torch.cat(parts["normals"], 1).contiguous(),
+                        torch.cat(parts["labels"]), torch.cat(parts["g2l"]).contiguous(), torch.cat(parts["search"]),
+                        torch.cat(parts["antipodal"]), torch.cat(parts["index"]).to(torch.int32))
+
+
 CR_MAX_RESOLUTION = 64                     # the compiled maximum of csrc/close_region.hip
 CR_DEFAULT_POINTS_PER_FRAME = 4096         # the default capacity is F * min(N, this)
 
