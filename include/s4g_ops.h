@@ -78,7 +78,10 @@ extern "C" {
  *     sensor cloud); s4g_contact_pairs_f32 / s4g_contact_pairs_workspace_bytes (the antipodal point pairs of an
  *     object cloud) and s4g_contact_pair_grade_f32 / s4g_contact_pair_grade_workspace_bytes (their rolled frames
  *     graded over that cloud, the kept frames and the object point of each: the per-object data the contact model's
- *     scenes are composed from). */
+ *     scenes are composed from); s4g_darboux_object_frames_f32 / s4g_darboux_object_frames_workspace_bytes (every
+ *     object point's Darboux frame and opposite frame) and s4g_darboux_object_grade_f32 /
+ *     s4g_darboux_object_grade_workspace_bytes (both graded over the object's own cloud: the per-object data the
+ *     curvature model's scenes are composed from). */
 #define S4G_ABI_VERSION 14
 
 /* ---------------------------------------------------------------------------
@@ -1197,6 +1200,65 @@ int s4g_contact_pair_grade_f32(const float *xyz_b3n, const int64_t *count_b, con
                                float *g2l_bf44, float *search_score_bf, float *antipodal_score_bf,
                                int32_t *frame_source_bf, int32_t *frame_point_index_bf, int64_t *frame_count_b,
                                int32_t *flags_b, void *workspace, size_t workspace_bytes, s4g_stream_t stream);
+
+/* The curvature (Darboux) model's per-object data (csrc/darboux.hip, csrc/darboux_object.hip): GenerateDarbouxObjectData
+ * of data_gen/data_generator/data_object_darboux_generator.py for every object of a batch, without host
+ * synchronisation.  Both entry points are run-to-run bit-identical and batch invariant: fixed summation order, integer
+ * atomics and ballots only, no floating-point atomics.  xyz, normals (B, 3, N) fp32; count_b (device, may be NULL): only
+ * the first count_b[b] points of object b are points.
+ *
+ * s4g_darboux_object_frames_f32 = _estimate_frame (:62-92) for every point.  Neighbours: squared distance < radius^2 in
+ * fp32, the point itself included, over the ordered cell grid of s4g_darboux_frames_f32 (a cell's records are read in
+ * ascending point index; points at or past count_b[b] are binned but never neighbours, so they should be finite: an
+ * object with a point that is not finite is scanned in index order -- the same sets, sums in another order).  In double:
+ * n = the neighbours' mean normal, normalised (:73-74); centroid = M mean with M = I - (n.n), the SCALAR n.n taken off
+ * every entry of the identity as the reference's 1-D `normal.T @ normal` does (:80-81), i.e. centroid_i = mean_i -
+ * (n.n) (mean_x + mean_y + mean_z); cov = sum of (normal - centroid)(normal - centroid)^T (:82-83), rounded to fp32
+ * once scaled by its trace; its smallest eigenvector by cyclic Jacobi in fp32 as s4g_darboux_frames_f32 runs it;
+ * minor = e - (e.n) n normalised with that entry point's sign rule; principal = minor x n.  frames_bn33 = columns
+ * [-n, -principal, minor], inv_frames_bn33 = [n, principal, minor], each rounded to fp32 once.  neighbours_bn int32 the
+ * neighbour count; flags_bn int32: 1 = estimated, 2 = degenerate or not finite, 4 = fewer than min_neighbours; with 2
+ * and 4, and for rows at or past count_b[b] (flags 0), both frames are ZERO (:75-78; not the identity of the view class).
+ * Limits: 1 <= N <= 65 536 (the grid's bitmap; S4G_EINVAL beyond), B <= 65 535.
+ * Workspace: s4g_darboux_object_frames_workspace_bytes(B, N); contents need not be initialised.
+ *
+ * s4g_darboux_object_grade_f32 = _estimate_grasp_quality with finger_hand_view and _antipodal_score (:94-247).  F frames
+ * per object at the points frame_index_bf (device, int32, may be NULL: frame f sits at point f; an index outside
+ * [0, count_b[b]) fails the row), each in two directions: frames_bf33 and inv_frames_bf33 (B, F, 3, 3), axes as columns.
+ * L depths, T rolls, S shifts of the hand along its thickness in the reference's loop order (at most 8, 16, 4).
+ *   params9 (HOST) = {HALF_BOTTOM_WIDTH, HALF_BOTTOM_SPACE, BACK_COLLISION_MARGIN, BACK_COLLISION_THRESHOLD,
+ *     FINGER_COLLISION_THRESHOLD, CLOSE_REGION_MIN_POINTS, NEIGHBOR_DEPTH, NUM_POINTS_THRESHOLD, HALF_HAND_THICKNESS +
+ *     max |dz|};  tables_3l2t2s (DEVICE) = dl [L], dl - BOTTOM_LENGTH [L], dl + FINGER_LENGTH [L], cos [T], sin [T] as
+ *     for s4g_local_search_f32, then -HALF_HAND_THICKNESS + dz [S], HALF_HAND_THICKNESS + dz [S] rounded once.
+ * Per (frame, direction): global -> local is [R^T | -R^T p] formed as s4g_local_search_f32 forms it (no fp32
+ * torch.inverse); a frame with mean |entry| < 1e-6 (:136) or that is not finite gets zero scores and fail = 1 (the
+ * reference raises).  Per depth: slab = count(lx < dl + FL & lx > dl - BL); below NUM_POINTS_THRESHOLD its T placements
+ * stay 0 (:153).  Per placement and shift, every inequality strict, on the rolled slab points: z = zz < HHT + dz & zz >
+ * -HHT + dz; back = z & |yy| < HBW & lx - dl < -margin; finger = z & HBS < |yy| < HBW; close = z & |yy| < HBS.  Shifts in
+ * order: skip on back > threshold, then on finger > threshold; close_num = close; skip on close_num < min points; else
+ * single = mean |n.y| left band * mean right band (:223-247; empty band: NaN), temp_antipodal += single / 3, temp_search
+ * += close_num / 3 (fp32 divisions and adds).  search = int(min(temp_search, close_num)) by truncation, antipodal =
+ * min(temp_antipodal, single) with NaN propagating: close_num and single are those of the LAST shift that got that far
+ * (:200,211,215-218).  There is no table gate and no label gate.
+ * Outputs: search_bf2lt int32, antipodal_bf2lt fp32 (B, F, 2, L, T); counts_bf2lts3 int32 (B, F, 2, L, T, S, 3) = {back,
+ * finger, close}, counted whatever the gates say; slab_bf2l int32 (B, F, 2, L); fail_bf2 int32 (B, F, 2).  A failed row
+ * reads 0 everywhere else.
+ * Cost: every object point is transformed for every row, N * 2 F * 18 flops; a point inside the cull costs 6 flops per
+ * roll.  Limits: N < 2^30, B * F * 2 * L * T * S <= 2^27, B <= 65 535 (S4G_EINVAL).
+ * Workspace: s4g_darboux_object_grade_workspace_bytes(B, N, F, L, T, S) (0 for lists beyond the maxima); contents need
+ * not be initialised; every launch of the call is a kernel. */
+size_t s4g_darboux_object_frames_workspace_bytes(int64_t B, int64_t N);
+int s4g_darboux_object_frames_f32(const float *xyz_b3n, const float *normals_b3n, const int64_t *count_b, int64_t B,
+                                  int64_t N, float radius, int32_t min_neighbours, float *frames_bn33,
+                                  float *inv_frames_bn33, int32_t *neighbours_bn, int32_t *flags_bn, void *workspace,
+                                  size_t workspace_bytes, s4g_stream_t stream);
+size_t s4g_darboux_object_grade_workspace_bytes(int64_t B, int64_t N, int64_t F, int64_t L, int64_t T, int64_t S);
+int s4g_darboux_object_grade_f32(const float *xyz_b3n, const float *normals_b3n, const int64_t *count_b,
+                                 const float *frames_bf33, const float *inv_frames_bf33, const int32_t *frame_index_bf,
+                                 int64_t B, int64_t N, int64_t F, int64_t L, int64_t T, int64_t S, const float *params9,
+                                 const float *tables_3l2t2s, int32_t *search_bf2lt, float *antipodal_bf2lt,
+                                 int32_t *counts_bf2lts3, int32_t *slab_bf2l, int32_t *fail_bf2, void *workspace,
+                                 size_t workspace_bytes, s4g_stream_t stream);
 
 /* ---- next row f3: cloud pre-processing on device -------------------------
  * Single-scene passes in front of the network (reference

@@ -155,6 +155,12 @@ SIGNATURES = {
     "s4g_contact_pair_grade_f32": (_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64,
                                           ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_double), _vp, _i64,
                                           _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "s4g_darboux_object_frames_workspace_bytes": (_sz, [_i64, _i64]),
+    "s4g_darboux_object_frames_f32": (_int, [_vp, _vp, _vp, _i64, _i64, _f32, _i32, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "s4g_darboux_object_grade_workspace_bytes": (_sz, [_i64, _i64, _i64, _i64, _i64, _i64]),
+    "s4g_darboux_object_grade_f32": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _i64,
+                                            ctypes.POINTER(ctypes.c_float), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz,
+                                            _vp]),
     "s4g_sort_pairs_workspace_bytes": (_sz, [_i64]),
     "s4g_sort_pairs_u32": (_int, [_vp, _vp, _i64, _int, _vp, _vp, _vp, _sz, _vp]),
     "s4g_exclusive_scan_workspace_bytes": (_sz, [_i64]),

@@ -111,10 +111,12 @@ __device__ __forceinline__ void jacobi_rotate(float& app, float& aqq, float& apq
 }
 
 // fn(normal x, y, z) for every point of scene b at squared distance < r2 of (x, y, z), in an order fixed by the scene.
-template <typename Fn>
+// LIM (the per-object frames): only the points whose index is below nlim are points.
+template <bool LIM = false, typename Fn>
 __device__ __forceinline__ void darboux_neighbours(bool grid, const DarbouxWs& ws, const float* __restrict__ p0,
                                                    const float* __restrict__ n0, int b, int N, float x, float y, float z,
-                                                   float ox, float oy, float oz, float r2, float inv_h, Fn fn) {
+                                                   float ox, float oy, float oz, float r2, float inv_h, Fn fn,
+                                                   int nlim = 0) {
   if (grid) {
     const int icx = grid_coord(x, ox, inv_h), icy = grid_coord(y, oy, inv_h), icz = grid_coord(z, oz, inv_h);
     const float4* __restrict__ rec = ws.rec + (size_t)b * N;
@@ -138,21 +140,22 @@ __device__ __forceinline__ void darboux_neighbours(bool grid, const DarbouxWs& w
         }
         for (int i = b0 - sh; i < e0 - sh; ++i) {
           const float4 q = rec[i];
-          if (dist2<false>(x, y, z, q.x, q.y, q.z) < r2) {
+          if (dist2<false>(x, y, z, q.x, q.y, q.z) < r2 && (!LIM || __float_as_int(q.w) < nlim)) {
             const float4 m = nrm[i];
             fn(m.x, m.y, m.z);
           }
         }
         for (int i = b1 - sh; i < e1 - sh; ++i) {
           const float4 q = rec[i];
-          if (dist2<false>(x, y, z, q.x, q.y, q.z) < r2) {
+          if (dist2<false>(x, y, z, q.x, q.y, q.z) < r2 && (!LIM || __float_as_int(q.w) < nlim)) {
             const float4 m = nrm[i];
             fn(m.x, m.y, m.z);
           }
         }
       }
   } else {
-    for (int i = 0; i < N; ++i)
+    const int n = LIM ? nlim : N;
+    for (int i = 0; i < n; ++i)
       if (dist2<false>(x, y, z, p0[i], p0[N + i], p0[2 * (size_t)N + i]) < r2) fn(n0[i], n0[N + i], n0[2 * (size_t)N + i]);
   }
 }
@@ -250,7 +253,138 @@ __global__ __launch_bounds__(DB_THREADS) void darboux_frames_kernel(
   flags[row] = flag;
 }
 
+// The per-object frames of GenerateDarbouxObjectData._estimate_frame (data_gen/data_generator/
+// data_object_darboux_generator.py:62-92): one thread per point of every object, over the same ordered grid.  It
+// differs from the view class in three places, all kept as written: the normal is the normalised MEAN of the
+// neighbours' normals (:73-74); the centroid is M @ mean with M = I - (n.n), a SCALAR taken off every entry of the
+// identity (:80, the 1-D `normal.T @ normal`), so centroid_i = mean_i - (n.n) (mean_x + mean_y + mean_z); and below
+// min_neighbours both frames are ZERO (:75-78).  frame = [-n, -principal, minor], inv_frame = [n, principal, minor].
+__global__ __launch_bounds__(DB_THREADS) void darboux_object_frames_kernel(
+    const float* __restrict__ xyz, const float* __restrict__ normals, const int64_t* __restrict__ obj_count, int N,
+    float r2, float inv_h, int min_neighbours, DarbouxWs ws, float* __restrict__ frames, float* __restrict__ inv_frames,
+    int32_t* __restrict__ count, int32_t* __restrict__ flags) {
+  const int b = blockIdx.y;
+  const int i = blockIdx.x * DB_THREADS + threadIdx.x;
+  if (i >= N) return;
+  const size_t row = (size_t)b * N + i;
+  const int nlim = obj_count ? (int)min((int64_t)N, max((int64_t)0, obj_count[b])) : N;
+  float o[9] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  int k = 0, flag = 0;
+  if (i < nlim) {
+    const float* __restrict__ p0 = xyz + (size_t)b * 3 * N;
+    const float* __restrict__ n0 = normals + (size_t)b * 3 * N;
+    const float px = p0[i], py = p0[N + i], pz = p0[2 * (size_t)N + i];
+    const bool own_bad = !(finite(px) && finite(py) && finite(pz));
+    const float ox = p0[0], oy = p0[N], oz = p0[2 * (size_t)N];
+    const bool grid = ws.grid.flags[b] == 0 && grid_coord_ok(px, ox, inv_h) && grid_coord_ok(py, oy, inv_h) &&
+                      grid_coord_ok(pz, oz, inv_h);
+    double sx = 0.0, sy = 0.0, sz = 0.0;
+    darboux_neighbours<true>(grid, ws, p0, n0, b, N, px, py, pz, ox, oy, oz, r2, inv_h, [&](float ax, float ay, float az) __attribute__((always_inline)) {
+      ++k;
+      sx += (double)ax;
+      sy += (double)ay;
+      sz += (double)az;
+    }, nlim);
+    const double ss = sx * sx + sy * sy + sz * sz;
+    if (own_bad || !(ss <= 1.7e308)) {
+      flag = 2;                       // the point or a neighbour's normal is not finite
+    } else if (k < min_neighbours) {
+      flag = 4;                       // :75-78, both frames stay zero
+    } else if (!(ss >= 1e-24)) {
+      flag = 2;                       // the mean normal vanishes: :74 divides by zero
+    } else {
+      const double mx = sx / (double)k, my = sy / (double)k, mz = sz / (double)k;     // :73
+      const double inv_m = 1.0 / sqrt(mx * mx + my * my + mz * mz);
+      const double nx = mx * inv_m, ny = my * inv_m, nz = mz * inv_m;                   // :74
+      const double nn = nx * nx + ny * ny + nz * nz;                                    // :80, the scalar
+      const double off = nn * (mx + my + mz);                                           // :81
+      const double cx = mx - off, cy = my - off, cz = mz - off;
+      double cxx = 0.0, cxy = 0.0, cxz = 0.0, cyy = 0.0, cyz = 0.0, czz = 0.0;
+      darboux_neighbours<true>(grid, ws, p0, n0, b, N, px, py, pz, ox, oy, oz, r2, inv_h, [&](float ax, float ay, float az) __attribute__((always_inline)) {
+        const double dx = (double)ax - cx, dy = (double)ay - cy, dz = (double)az - cz;  // :82-83
+        cxx += dx * dx; cxy += dx * dy; cxz += dx * dz;
+        cyy += dy * dy; cyz += dy * dz; czz += dz * dz;
+      }, nlim);
+      const double tr = cxx + cyy + czz;
+      const double sc = tr > 0.0 ? 1.0 / tr : 0.0;
+      float a00 = (float)(cxx * sc), a01 = (float)(cxy * sc), a02 = (float)(cxz * sc);
+      float a11 = (float)(cyy * sc), a12 = (float)(cyz * sc), a22 = (float)(czz * sc);
+      float v00 = 1.f, v01 = 0.f, v02 = 0.f, v10 = 0.f, v11 = 1.f, v12 = 0.f, v20 = 0.f, v21 = 0.f, v22 = 1.f;
+      for (int s = 0; s < DB_SWEEPS; ++s) {
+        jacobi_rotate(a00, a11, a01, a02, a12, v00, v01, v10, v11, v20, v21);
+        jacobi_rotate(a00, a22, a02, a01, a12, v00, v02, v10, v12, v20, v22);
+        jacobi_rotate(a11, a22, a12, a01, a02, v01, v02, v11, v12, v21, v22);
+      }
+      double ex = (double)v00, ey = (double)v10, ez = (double)v20;
+      float small = a00;
+      if (a11 < small) { small = a11; ex = (double)v01; ey = (double)v11; ez = (double)v21; }
+      if (a22 < small) { small = a22; ex = (double)v02; ey = (double)v12; ez = (double)v22; }
+      const double en = ex * nx + ey * ny + ez * nz;                                    // :86
+      double ux = ex - en * nx, uy = ey - en * ny, uz = ez - en * nz;
+      const double uu = ux * ux + uy * uy + uz * uz;
+      if (!(uu >= 1e-12 && uu <= 1.7e308 && fabs(tr) <= 1.7e308)) {
+        flag = 2;
+      } else {
+        double lead = ux;             // the sign rule of darboux_frames_kernel
+        if (fabs(uy) > fabs(lead)) lead = uy;
+        if (fabs(uz) > fabs(lead)) lead = uz;
+        const double inv = (lead < 0.0 ? -1.0 : 1.0) / sqrt(uu);
+        ux *= inv; uy *= inv; uz *= inv;                                                // :87
+        const double qx = uy * nz - uz * ny, qy = uz * nx - ux * nz, qz = ux * ny - uy * nx;   // :88
+        o[0] = (float)nx; o[1] = (float)qx; o[2] = (float)ux;                           // :91, axes as columns
+        o[3] = (float)ny; o[4] = (float)qy; o[5] = (float)uy;
+        o[6] = (float)nz; o[7] = (float)qz; o[8] = (float)uz;
+        flag = 1;
+      }
+    }
+  }
+  float* __restrict__ fr = frames + row * 9;
+  float* __restrict__ iv = inv_frames + row * 9;
+#pragma unroll
+  for (int j = 0; j < 9; ++j) {
+    iv[j] = o[j];
+    fr[j] = (j % 3 == 2 || flag != 1) ? o[j] : -o[j];                                   // :90 (a zero frame stays +0)
+  }
+  count[row] = k;
+  flags[row] = flag;
+}
+
 }  // namespace s4g
+
+extern "C" size_t s4g_darboux_object_frames_workspace_bytes(int64_t B, int64_t N) {
+  if (B <= 0) return 0;
+  return s4g::darboux_ws(nullptr, B, N, nullptr);
+}
+
+extern "C" int s4g_darboux_object_frames_f32(const float* xyz_b3n, const float* normals_b3n, const int64_t* count_b,
+                                             int64_t B, int64_t N, float radius, int32_t min_neighbours,
+                                             float* frames_bn33, float* inv_frames_bn33, int32_t* neighbours_bn,
+                                             int32_t* flags_bn, void* workspace, size_t workspace_bytes,
+                                             s4g_stream_t stream) {
+  using namespace s4g;
+  if (B < 0 || B > 65535 || N < 1 || N > GR_MAX_POINTS) return S4G_EINVAL;
+  if (!(radius > 0.f) || !(radius < 1e18f) || min_neighbours < 1) return S4G_EINVAL;
+  if (B == 0) return S4G_OK;
+  if (!xyz_b3n || !normals_b3n || !frames_bn33 || !inv_frames_bn33 || !neighbours_bn || !flags_bn) return S4G_EINVAL;
+  hipStream_t st = (hipStream_t)stream;
+  const float r2 = radius * radius;
+  const float h = radius * (1.0f + 1.0f / 256.0f);
+  const float inv_h = 1.0f / h;
+  DarbouxWs w = {};
+  const size_t need = darboux_ws(workspace, B, N, nullptr);
+  if (!workspace || workspace_bytes < need) return S4G_EWORKSPACE;
+  darboux_ws(workspace, B, N, &w);
+  if (int rc = launch_grid_build(xyz_b3n, B, N, inv_h, w.grid, st, false)) return rc;
+  hipLaunchKernelGGL(darboux_order_kernel,
+                     dim3((unsigned)((N + DB_ORDER_THREADS - 1) / DB_ORDER_THREADS), GR_RANGES, (unsigned)B),
+                     dim3(DB_ORDER_THREADS), 0, st, xyz_b3n, normals_b3n, (int)N, inv_h, w);
+  S4G_LAUNCH_CHECK();
+  hipLaunchKernelGGL(darboux_object_frames_kernel, dim3((unsigned)((N + DB_THREADS - 1) / DB_THREADS), (unsigned)B),
+                     dim3(DB_THREADS), 0, st, xyz_b3n, normals_b3n, count_b, (int)N, r2, inv_h, (int)min_neighbours, w,
+                     frames_bn33, inv_frames_bn33, neighbours_bn, flags_bn);
+  S4G_LAUNCH_CHECK();
+  return S4G_OK;
+}
 
 extern "C" size_t s4g_darboux_frames_workspace_bytes(int64_t B, int64_t N, int64_t F) {
   (void)F;

@@ -1711,6 +1711,304 @@ def compose_contact_scene(objects, poses, labels=None):
                         torch.cat(parts["antipodal"]), torch.cat(parts["index"]).to(torch.int32))
 
 
+DO_MAX_DEPTHS, DO_MAX_ANGLES, DO_MAX_SHIFTS = 8, 16, 4     # the compiled maxima of csrc/darboux_object.hip
+DO_MAX_POINTS = 65536                      # the frame kernel's cell grid (csrc/grid.h: GR_MAX_POINTS)
+DO_FLAG_ESTIMATED, DO_FLAG_DEGENERATE, DO_FLAG_FEW = 1, 2, 4
+
+
+@dataclass
+class DarbouxObjectConfig:
+    """The constants of the curvature model's per-object data (data_gen/data_generator/data_object_darboux_generator.py
+    and data_gen/configs/config.py:23-56): those of `LocalSearchConfig` that `finger_hand_view` reads, the shifts of the
+    hand along its thickness in the reference's loop order (:181), CURVATURE_RADIUS and the neighbour floor (:72,75)."""
+    num_points_threshold: float = 8
+    length_search: tuple = (-0.08, -0.06, -0.04, -0.02)
+    theta_search_deg: tuple = tuple(range(-90, 90, 15))
+    shift_search: tuple = (-0.02, 0.02, 0)
+    back_collision_threshold: float = 0 * math.sqrt(8)
+    back_collision_margin: float = 0.0
+    finger_collision_threshold: float = 0
+    close_region_min_points: float = 10
+    neighbor_depth: float = 0.005
+    half_bottom_width: float = 0.057
+    bottom_length: float = 0.08
+    finger_width: float = 0.023
+    half_hand_thickness: float = 0.012
+    finger_length: float = 0.09
+    radius: float = CURVATURE_RADIUS
+    min_neighbours: int = 5
+
+    @property
+    def half_bottom_space(self):
+        return self.half_bottom_width - self.finger_width
+
+    @property
+    def shape(self):
+        """(L, T, S): depths, rolls per depth, shifts."""
+        return len(self.length_search), len(self.theta_search_deg), len(self.shift_search)
+
+    def check(self):
+        L, T, S = self.shape
+        if not (1 <= L <= DO_MAX_DEPTHS and 1 <= T <= DO_MAX_ANGLES and 1 <= S <= DO_MAX_SHIFTS):
+            raise ValueError("need 1..%d depths, 1..%d angles and 1..%d shifts, got %d, %d and %d"
+                             % (DO_MAX_DEPTHS, DO_MAX_ANGLES, DO_MAX_SHIFTS, L, T, S))
+        if not float(self.radius) > 0.0:
+            raise ValueError("radius must be positive, got %r" % (self.radius,))
+        if int(self.min_neighbours) < 1:
+            raise ValueError("min_neighbours must be at least 1, got %r" % (self.min_neighbours,))
+
+    def tables(self):
+        """`LocalSearchConfig.tables` for the depths and rolls, plus the z window of every shift: `zlo`, `zhi` (S) =
+        -HALF_HAND_THICKNESS + dz, HALF_HAND_THICKNESS + dz in Python floats, rounded to fp32 once (:183-184)."""
+        self.check()
+        tb = LocalSearchConfig(length_search=tuple(self.length_search), theta_search_deg=tuple(self.theta_search_deg),
+                               bottom_length=self.bottom_length, finger_length=self.finger_length).tables()
+        hht = self.half_hand_thickness
+        tb["zlo"] = torch.tensor([-hht + float(d) for d in self.shift_search], dtype=torch.float64).to(torch.float32)
+        tb["zhi"] = torch.tensor([hht + float(d) for d in self.shift_search], dtype=torch.float64).to(torch.float32)
+        return tb
+
+
+@dataclass
+class ObjectFrames:
+    """What `estimate_object_frames` returns, one row per point: `frames`, `inv_frames` (B, N, 3, 3) fp32 with the axes
+    as columns, `neighbours` (B, N) int32, `flags` (B, N) int32 (`DO_FLAG_*`)."""
+    frames: torch.Tensor
+    inv_frames: torch.Tensor
+    neighbours: torch.Tensor
+    flags: torch.Tensor
+    unbatched: bool = False
+
+    estimated = property(lambda self: (self.flags & DO_FLAG_ESTIMATED) != 0)
+    degenerate = property(lambda self: (self.flags & DO_FLAG_DEGENERATE) != 0)
+
+
+@dataclass
+class ObjectGrades:
+    """What `grade_object_frames` returns, direction 0 = `frames`, 1 = `inv_frames`: `search_score` int32 and
+    `antipodal_score` fp32 (B, F, 2, L, T), `counts` (B, F, 2, L, T, S, 3) int32 = {back, finger, close}, `slab_count`
+    (B, F, 2, L) int32, `fail_i32` (B, F, 2)."""
+    search_score: torch.Tensor
+    antipodal_score: torch.Tensor
+    counts: torch.Tensor
+    slab_count: torch.Tensor
+    fail_i32: torch.Tensor
+    config: DarbouxObjectConfig
+    unbatched: bool = False
+
+    fail = property(lambda self: self.fail_i32 != 0)
+
+
+def estimate_object_frames(points, normals, count=None, config=None):
+    """`GenerateDarbouxObjectData._estimate_frame` (data_gen/data_generator/data_object_darboux_generator.py:62-92),
+    which loops over the points with a kd-tree radius query and an `eigh` each, for every point of every object in one
+    sync-free, graph-capturable call -> `ObjectFrames`.  points, normals (B, 3, N) fp32, N <= 65 536; an unbatched
+    cloud gets a leading 1; count (B,) on the device (optional): the points of object b are its first count[b], the
+    other rows read zero frames.  Neighbours: squared distance < radius^2 in fp32, the point itself included.
+
+    Decision 3 of the per-object stage: `M = np.eye(3) - normal.T @ normal` (:80) has a 1-D `normal`, so it is the
+    identity with the SCALAR n.n taken off every entry, not the projector of the view class; it is reproduced as
+    written, with n the normalised mean of the neighbours' normals and everything up to the covariance in double (the
+    reference's shipped object data was made this way).  frame = [-n, -principal, minor], inv_frame = [n, principal,
+    minor].  Below `min_neighbours` both are ZERO (:75-78), not the identity the view class leaves.  The eigenvector's
+    sign follows `estimate_frames`; a degenerate or non-finite row gives zero frames and `DO_FLAG_DEGENERATE`."""
+    cfg = config or DarbouxObjectConfig()
+    cfg.check()
+    xyz, nrm, cnt, unbatched = _object_cloud(points, normals, count)
+    B, _, N = xyz.shape
+    if N > DO_MAX_POINTS:
+        raise ValueError("an object cloud holds at most %d points, got %d" % (DO_MAX_POINTS, N))
+    dev = xyz.device
+    if cnt is not None:
+        # the columns past count are binned with the points (never read as neighbours): fold them onto the object's
+        # own points, so that they are finite and spread over its cells
+        col = torch.arange(N, device=dev).view(1, N)
+        src = torch.where(col < cnt.view(B, 1), col, col % cnt.clamp(min=1).view(B, 1))
+        xyz = torch.gather(xyz, 2, src.view(B, 1, N).expand(B, 3, N)).contiguous()
+    out = ObjectFrames(torch.empty((B, N, 3, 3), dtype=torch.float32, device=dev),
+                       torch.empty((B, N, 3, 3), dtype=torch.float32, device=dev),
+                       torch.empty((B, N), dtype=torch.int32, device=dev),
+                       torch.empty((B, N), dtype=torch.int32, device=dev), unbatched)
+    ws, nbytes = _workspace(_cabi.lib().s4g_darboux_object_frames_workspace_bytes(B, N), dev)
+    with torch.cuda.device(dev):
+        rc = _cabi.lib().s4g_darboux_object_frames_f32(
+            xyz.data_ptr(), nrm.data_ptr(), None if cnt is None else cnt.data_ptr(), B, N, float(cfg.radius),
+            int(cfg.min_neighbours), out.frames.data_ptr(), out.inv_frames.data_ptr(), out.neighbours.data_ptr(),
+            out.flags.data_ptr(), ws.data_ptr(), nbytes, _F._stream())
+    _cabi.check(rc, "darboux_object_frames")
+    return out
+
+
+def _object_grade_args(cfg):
+    """(params9 as a ctypes array, the table tensor on the CPU) of `s4g_darboux_object_grade_f32`."""
+    tb = cfg.tables()
+    zmax = cfg.half_hand_thickness + max(abs(float(d)) for d in cfg.shift_search)
+    params = (ctypes.c_float * 9)(cfg.half_bottom_width, cfg.half_bottom_space, cfg.back_collision_margin,
+                                  cfg.back_collision_threshold, cfg.finger_collision_threshold,
+                                  cfg.close_region_min_points, cfg.neighbor_depth, cfg.num_points_threshold, zmax)
+    return params, torch.cat([tb["depth"], tb["lo"], tb["hi"], tb["cos"], tb["sin"], tb["zlo"], tb["zhi"]])
+
+
+def grade_object_frames(points, normals, frames, inv_frames, config=None, count=None, frame_index=None):
+    """`GenerateDarbouxObjectData._estimate_grasp_quality` with `finger_hand_view` and `_antipodal_score`
+    (data_object_darboux_generator.py:94-247): every frame and its opposite frame against the object's own cloud, L
+    depths x T rolls x S shifts each, for every frame of every object in one sync-free, graph-capturable call ->
+    `ObjectGrades`.  points, normals (B, 3, N) fp32; frames, inv_frames (B, F, 3, 3) fp32 with the axes as columns;
+    frame_index (B, F) int32 on the device (optional): the point each frame sits at (default: F = N, frame f at point
+    f; an index outside the object fails the row); count (B,) as for `estimate_object_frames`.
+
+    Decisions (INTEGRATION.md has all five).  (1) The accumulator pairs of :179-180 -- `a, b = torch.zeros(1, ...)`,
+    which raises as written -- are two fp32 scalars that start at 0.  (2) A zero (mean |entry| < 1e-6) or non-finite
+    frame gets zero scores and `fail`; the reference raises on the early return of :137.  (4) Global -> local is
+    [R^T | -R^T p], not `torch.inverse` in fp32.  (5) Everything else as written, in the reference's order: no table
+    gate and no label gate; a depth whose slab holds fewer than NUM_POINTS_THRESHOLD points leaves its placements 0;
+    shifts in the order given with the window (-HHT + dz, HHT + dz); per shift the gates back > threshold, finger >
+    threshold, close < CLOSE_REGION_MIN_POINTS; `close_region_point_num` is overwritten by every shift that passes the
+    two collision gates and `single_antipodal` by every shift that passes all three, and the results are
+    min(temp_search, close_region_point_num) and min(temp_antipodal, single_antipodal): the last-shift quirk that
+    `grade_contact_pairs` carries for its own class; `temp += n / 3` in fp32 in shift order; `search_score` is int32 by
+    truncation; a close region whose points share one y gives a NaN antipodal score that propagates."""
+    cfg = config or DarbouxObjectConfig()
+    cfg.check()
+    xyz, nrm, cnt, unbatched = _object_cloud(points, normals, count)
+    B, _, N = xyz.shape
+    dev = xyz.device
+    for name, t in (("frames", frames), ("inv_frames", inv_frames)):
+        if not isinstance(t, torch.Tensor) or t.device.type != "cuda":
+            raise RuntimeError("%s must be a CUDA tensor (there is no CPU fallback)" % name)
+    if frames.dim() == 3:
+        frames, inv_frames = frames[None], inv_frames[None]
+        frame_index = frame_index[None] if frame_index is not None and frame_index.dim() == 1 else frame_index
+    frm, inv = _F._f32c(frames, "frames"), _F._f32c(inv_frames, "inv_frames")
+    if frm.dim() != 4 or frm.size(0) != B or tuple(frm.shape[2:]) != (3, 3) or frm.device != dev:
+        raise RuntimeError("frames must be (B, F, 3, 3) on the device of points")
+    if tuple(inv.shape) != tuple(frm.shape) or inv.device != dev:
+        raise RuntimeError("inv_frames must be (B, F, 3, 3) like frames")
+    F = frm.size(1)
+    if frame_index is None:
+        if F != N:
+            raise RuntimeError("without a frame_index there is one frame per point: frames must be (B, N, 3, 3)")
+    else:
+        if not isinstance(frame_index, torch.Tensor) or frame_index.device != dev or frame_index.dtype != torch.int32:
+            raise RuntimeError("frame_index must be an int32 tensor on the device of points")
+        if tuple(frame_index.shape) != (B, F):
+            raise RuntimeError("frame_index must be (B, F)")
+        frame_index = frame_index.contiguous()
+    L, T, S = cfg.shape
+    params, table = _object_grade_args(cfg)
+    tables = _small_on_device(table, torch.float32, dev)
+    out = ObjectGrades(torch.empty((B, F, 2, L, T), dtype=torch.int32, device=dev),
+                       torch.empty((B, F, 2, L, T), dtype=torch.float32, device=dev),
+                       torch.empty((B, F, 2, L, T, S, 3), dtype=torch.int32, device=dev),
+                       torch.empty((B, F, 2, L), dtype=torch.int32, device=dev),
+                       torch.empty((B, F, 2), dtype=torch.int32, device=dev), cfg, unbatched)
+    ws, nbytes = _workspace(_cabi.lib().s4g_darboux_object_grade_workspace_bytes(B, N, F, L, T, S), dev)
+    with torch.cuda.device(dev):
+        rc = _cabi.lib().s4g_darboux_object_grade_f32(
+            xyz.data_ptr(), nrm.data_ptr(), None if cnt is None else cnt.data_ptr(), frm.data_ptr(), inv.data_ptr(),
+            None if frame_index is None else frame_index.data_ptr(), B, N, F, L, T, S, params, tables.data_ptr(),
+            out.search_score.data_ptr(), out.antipodal_score.data_ptr(), out.counts.data_ptr(),
+            out.slab_count.data_ptr(), out.fail_i32.data_ptr(), ws.data_ptr(), nbytes, _F._stream())
+    _cabi.check(rc, "darboux_object_grade")
+    return out
+
+
+@dataclass
+class ObjectDarbouxData:
+    """What `label_darboux_object` returns: the cloud as given (`points`, `normals` (B, 3, N), `count` (B,) or None),
+    its `frames` (`ObjectFrames`) and their `grades` (`ObjectGrades`)."""
+    points: torch.Tensor
+    normals: torch.Tensor
+    count: torch.Tensor
+    frames: ObjectFrames
+    grades: ObjectGrades
+    unbatched: bool = False
+
+    def dump(self, b=0):
+        """The dictionary the reference pickles per object (:50-57, :125-128) for object b, as numpy.  Reads the count
+        on the host."""
+        n = self.points.shape[2] if self.count is None else int(self.count[b])
+        g = self.grades
+        return {"cloud": self.points[b, :, :n].t().cpu().numpy(),
+                "normal": self.normals[b, :, :n].t().cpu().numpy(),
+                "frame": self.frames.frames[b, :n].cpu().numpy(),
+                "inv_frame": self.frames.inv_frames[b, :n].cpu().numpy(),
+                "search_score": g.search_score[b, :n, 0].cpu().numpy(),
+                "inv_search_score": g.search_score[b, :n, 1].cpu().numpy(),
+                "antipodal_score": g.antipodal_score[b, :n, 0].cpu().numpy(),
+                "inv_antipodal_score": g.antipodal_score[b, :n, 1].cpu().numpy()}
+
+
+def label_darboux_object(points, normals, config=None, count=None):
+    """`GenerateDarbouxObjectData.run_loop` from the sampled cloud on (data_object_darboux_generator.py:52-57): object
+    cloud in, every point's Darboux frame, its opposite frame and the grasp scores of both out, in one sync-free,
+    graph-capturable call on the library's stream -> `ObjectDarbouxData`.  `estimate_object_frames` then
+    `grade_object_frames`; see both for the arguments and the decisions."""
+    cfg = config or DarbouxObjectConfig()
+    xyz, nrm, cnt, unbatched = _object_cloud(points, normals, count)
+    fr = estimate_object_frames(xyz, nrm, cnt, cfg)
+    g = grade_object_frames(xyz, nrm, fr.frames, fr.inv_frames, cfg, cnt)
+    fr.unbatched = g.unbatched = unbatched
+    return ObjectDarbouxData(xyz, nrm, cnt, fr, g, unbatched)
+
+
+@dataclass
+class DarbouxScene:
+    """What `compose_darboux_scene` returns, one scene of M points: `points`, `normals` (3, M) fp32, `labels` (M,)
+    int32, `frames`, `inv_frames` (M, 3, 3) fp32, `search_score`, `inv_search_score` (M, L, T) int32,
+    `antipodal_score`, `inv_antipodal_score` (M, L, T) fp32."""
+    points: torch.Tensor
+    normals: torch.Tensor
+    labels: torch.Tensor
+    frames: torch.Tensor
+    inv_frames: torch.Tensor
+    search_score: torch.Tensor
+    inv_search_score: torch.Tensor
+    antipodal_score: torch.Tensor
+    inv_antipodal_score: torch.Tensor
+
+    def dump(self):
+        """The dictionary the reference pickles per scene (data_scene_generator.py:105-107), as numpy, without `color`."""
+        return {"cloud": self.points.t().cpu().numpy(), "frame": self.frames.cpu().numpy(),
+                "label": self.labels.cpu().numpy(), "normal": self.normals.t().cpu().numpy(),
+                "inv_frame": self.inv_frames.cpu().numpy(), "search_score": self.search_score.cpu().numpy(),
+                "antipodal_score": self.antipodal_score.cpu().numpy(),
+                "inv_search_score": self.inv_search_score.cpu().numpy(),
+                "inv_antipodal_score": self.inv_antipodal_score.cpu().numpy()}
+
+
+def compose_darboux_scene(objects, poses, labels=None):
+    """`GenerateDarbouxScene.generate_single_scene` (data_gen/data_generator/data_scene_generator.py:59-107) in torch
+    on the device: objects, a list of (`ObjectDarbouxData`, b) or of `ObjectDarbouxData` (object 0); poses, one
+    (x, y, z, qw, qx, qy, qz) each; labels, one int each (default 0, 1, ...).  Points are moved by the pose, normals and
+    both frame sets by its rotation (in fp32; the reference keeps float64), the four score arrays and the labels are
+    concatenated -> `DarbouxScene`.  Reads every object's count on the host."""
+    if len(objects) != len(poses) or not objects:
+        raise ValueError("one pose per object, at least one object")
+    keys = ("points", "normals", "labels", "frames", "inv_frames", "search", "inv_search", "antipodal", "inv_antipodal")
+    parts = {k: [] for k in keys}
+    for k, (obj, pose) in enumerate(zip(objects, poses)):
+        obj, b = obj if isinstance(obj, tuple) else (obj, 0)
+        dev = obj.points.device
+        n = obj.points.shape[2] if obj.count is None else int(obj.count[b])
+        m32 = pose_matrix(pose).to(torch.float32).to(dev)
+        rot = m32[:3, :3]
+        parts["points"].append(rot @ obj.points[b, :, :n] + m32[:3, 3:])
+        parts["normals"].append(rot @ obj.normals[b, :, :n])
+        parts["labels"].append(torch.full((n,), k if labels is None else int(labels[k]), dtype=torch.int32, device=dev))
+        parts["frames"].append(torch.matmul(rot, obj.frames.frames[b, :n]))
+        parts["inv_frames"].append(torch.matmul(rot, obj.frames.inv_frames[b, :n]))
+        parts["search"].append(obj.grades.search_score[b, :n, 0])
+        parts["inv_search"].append(obj.grades.search_score[b, :n, 1])
+        parts["antipodal"].append(obj.grades.antipodal_score[b, :n, 0])
+        parts["inv_antipodal"].append(obj.grades.antipodal_score[b, :n, 1])
+    return DarbouxScene(torch.cat(parts["points"], 1).contiguous(), torch.cat(parts["normals"], 1).contiguous(),
+                        torch.cat(parts["labels"]), torch.cat(parts["frames"]).contiguous(),
+                        torch.cat(parts["inv_frames"]).contiguous(), torch.cat(parts["search"]).contiguous(),
+                        torch.cat(parts["inv_search"]).contiguous(), torch.cat(parts["antipodal"]).contiguous(),
+                        torch.cat(parts["inv_antipodal"]).contiguous())
+
+
 CR_MAX_RESOLUTION = 64                     # the compiled maximum of csrc/close_region.hip
 CR_DEFAULT_POINTS_PER_FRAME = 4096         # the default capacity is F * min(N, this)
 
