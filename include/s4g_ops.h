@@ -81,7 +81,10 @@ extern "C" {
  *     scenes are composed from); s4g_darboux_object_frames_f32 / s4g_darboux_object_frames_workspace_bytes (every
  *     object point's Darboux frame and opposite frame) and s4g_darboux_object_grade_f32 /
  *     s4g_darboux_object_grade_workspace_bytes (both graded over the object's own cloud: the per-object data the
- *     curvature model's scenes are composed from). */
+ *     curvature model's scenes are composed from); s4g_precomputed_select_f32 (every view point's frame, scores and
+ *     recommended placements looked up at its nearest point of such a scene) and s4g_precomputed_search_f32 /
+ *     s4g_precomputed_search_workspace_bytes (the collision check of the recommended placements against the dense
+ *     scene: the view stage of the curvature model's fast label pipeline). */
 #define S4G_ABI_VERSION 14
 
 /* ---------------------------------------------------------------------------
@@ -1128,6 +1131,74 @@ int s4g_contact_select_f32(const int32_t *nearest_bn, const float *cloud_b3n, co
                            const int32_t *valid_bf, const float *search_bf, const float *antipodal_bf, int64_t B,
                            int64_t N, int64_t M, int64_t F, float *normals_b3n, int32_t *best_frame_bn,
                            float *point_score_bn, int32_t *valid_index_bn, int64_t *count_b, s4g_stream_t stream);
+
+/* The view stage of the curvature model's fast label pipeline (csrc/precomputed_view.hip; added under ABI 14 with no
+ * layout change): TorchPrecomputedSingleViewPointCloud.run_score
+ * (data_gen/pcd_classes/torch_precomputed_single_view_point_cloud.py), without host synchronisation.  Both entry points
+ * are run-to-run bit-identical and batch invariant: integer atomics and ballots only, no floating-point atomics.
+ * P = L * T placements per point, index = depth * T + roll; 1 <= L <= 8, 1 <= T <= 16 (S4G_EINVAL otherwise).
+ *
+ * s4g_precomputed_select_f32 = _find_match (:130-178) with magic_formula (:180-185), one thread per view point.
+ * nearest (B, N) int32 from s4g_match_nearest_f32 (run on the noise-free reference cloud); cloud (B, 3, N) the noisy
+ * view; scene_normals (B, 3, M); camera (B, 3) the camera location; scene_frames (B, M, 3, 3) with the axes as COLUMNS;
+ * search, inv_search (B, M, P) int32 and antipodal, inv_antipodal (B, M, P) fp32 the scene's scores.  Per view point,
+ * i = nearest, or -1 where the noisy point is not finite:
+ *   n = the normal of i by the rule of s4g_contact_select_f32: the scene normal, or (0, 0, 1) without one, n / |n| in
+ *     double, turned towards the camera seen from the NOISY point; normals_b3n holds it rounded to fp32 once;
+ *   flipped = n . frame[:, 0] > 0 (:163), formed in double from the unrounded n and the fp32 frame column;
+ *   frames = the scene frame of i, columns 0 and 1 negated where flipped (:166); the scene's inv_frame is not read;
+ *   pre_search / pre_antipodal = the scene's scores of i, the inv_* arrays where flipped (:167-170);
+ *   mask = (double)pre_search > search_threshold and (double)pre_antipodal > antipodal_threshold (:181-183: numpy
+ *     compares in float64, so the fp32 value 0.300000012 passes > 0.3);
+ *   candidate = i >= 0, some mask bit set, and the noisy z > sample_region in fp32 (:172-174).
+ *   i < 0: normal (0, 0, 1) turned towards the camera, the identity frame, scores 0, mask 0, no candidate.
+ * Outputs: normals_b3n fp32 (B, 3, N); flipped_bn int32 (B, N); frames_bn33 fp32 (B, N, 3, 3); pre_search_bnp int32 and
+ * pre_antipodal_bnp fp32 (B, N, P); mask_bnp bytes 0 / 1 (B, N, P); candidate_bn int32 (B, N); frame_index_bn int32
+ * (B, N) the candidates in ascending order, then -1; frame_count_b int64 (B).  N, M < 2^30, M >= 1, B <= 65 535.
+ * No workspace.
+ *
+ * s4g_precomputed_search_f32 = finger_hand (:277-396) with _table_collision_check (:258-275) for F candidate rows per
+ * scene.  points (B, F, 3) the noisy view points, frames (B, F, 3, 3) (axes as COLUMNS), mask bytes, pre_search int32
+ * and pre_antipodal fp32 (B, F, P) as the select call writes them; xyz (B, 3, M) fp32 and labels (B, M) int32 the dense
+ * scene, a NaN point of which is in no region and in no slab; frame_count_b (device, may be NULL): only the first
+ * frame_count_b[b] rows of scene b are frames.
+ * params13 (HOST pointer) = {FINGER_LENGTH, BOTTOM_LENGTH, HALF_HAND_THICKNESS, HALF_BOTTOM_WIDTH, HALF_BOTTOM_SPACE,
+ *   BACK_COLLISION_MARGIN, BACK_COLLISION_THRESHOLD, FINGER_COLLISION_THRESHOLD, CLOSE_REGION_MIN_POINTS,
+ *   TABLE_HEIGHT + TABLE_COLLISION_OFFSET, NUM_POINTS_THRESHOLD, valid_search_min (1, :384), valid_antipodal_min
+ *   (0.1, :385)}; tables_3l2t (DEVICE pointer) as for s4g_local_search_f32.
+ * The only frame gate is mean |frame| < 1e-6 (:295): the reach gate of s4g_local_search_f32 does not exist in this
+ * class.  [R^T | -R^T p], the table verdicts, the roll and every region test are those of s4g_local_search_f32, the
+ * same operations in the same order: with an all-true mask the counts are its counts bit for bit.
+ * A depth without a mask bit is skipped before its slab is counted (:305): slab 0.  A placement is graded when its
+ * mask bit is set and its table verdict is clear (:327); its gates in the reference's order, every inequality strict:
+ * slab >= params[10] (:312), back <= params[6] (:342), finger <= params[7] (:353), close >= params[8] (:363), one
+ * label (:369).  A placement that passes takes search_score = pre_search, antipodal = pre_antipodal, objects_label =
+ * the region's label; every other one 0 / 0 / no_label.
+ * Outputs: ints_bfp6 int32 (B, F, P, 6) = {search_score, objects_label, back, finger, close, table_collision}, the
+ *   counts 0 for a placement that was not graded; scores_bfp fp32 (B, F, P); slab_bfl int32 (B, F, L);
+ *   valid_bf int32 (B, F): 0 where max(search_score) < params[11] or max(antipodal) < params[12] (:384), or the gate
+ *   failed; valid_index_bf int32 (B, F) ascending, then -1; count_b int64 (B).
+ * Every frame's row holds its own results only (the reference does not clear slot valid_grasp after a rejected frame).
+ * M < 2^30, B and F <= 65 535.  Cost: every scene point is transformed for every frame with a mask bit, M * F * 18
+ * flops; one sweep of the cloud, no second scan.
+ * Workspace: s4g_precomputed_search_workspace_bytes(B, M, F, L, T) bytes, 256-byte aligned; contents need not be
+ * initialised; every launch of the call is a kernel. */
+int s4g_precomputed_select_f32(const int32_t *nearest_bn, const float *cloud_b3n, const float *scene_normals_b3m,
+                               const float *camera_b3, const float *scene_frames_bm33, const int32_t *search_bmp,
+                               const int32_t *inv_search_bmp, const float *antipodal_bmp,
+                               const float *inv_antipodal_bmp, int64_t B, int64_t N, int64_t M, int64_t L, int64_t T,
+                               double search_threshold, double antipodal_threshold, float sample_region,
+                               float *normals_b3n, int32_t *flipped_bn, float *frames_bn33, int32_t *pre_search_bnp,
+                               float *pre_antipodal_bnp, uint8_t *mask_bnp, int32_t *candidate_bn,
+                               int32_t *frame_index_bn, int64_t *frame_count_b, s4g_stream_t stream);
+size_t s4g_precomputed_search_workspace_bytes(int64_t B, int64_t M, int64_t F, int64_t L, int64_t T);
+int s4g_precomputed_search_f32(const float *points_bf3, const float *frames_bf33, const uint8_t *mask_bfp,
+                               const int32_t *pre_search_bfp, const float *pre_antipodal_bfp, const float *xyz_b3m,
+                               const int32_t *labels_bm, int64_t B, int64_t M, int64_t F, int64_t L, int64_t T,
+                               const float *params13, int32_t no_label, const float *tables_3l2t,
+                               const int64_t *frame_count_b, int32_t *ints_bfp6, float *scores_bfp, int32_t *slab_bfl,
+                               int32_t *valid_bf, int32_t *valid_index_bf, int64_t *count_b, void *workspace,
+                               size_t workspace_bytes, s4g_stream_t stream);
 
 /* The contact model's per-object frames (csrc/contact_pairs.hip): GenerateContactObjectData of
  * data_gen/data_generator/data_object_contact_point_generator.py for every object of a batch, without host

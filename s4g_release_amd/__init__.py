@@ -95,6 +95,28 @@ def compose_contact_scene(*args, **kwargs):
     return _compose(*args, **kwargs)
 
 
+def match_scene_frames(*args, **kwargs):
+    """Every view point's frame, scores and recommended placements, looked up at its nearest point of a
+    `DarbouxScene`.  See `postprocess.match_scene_frames`."""
+    from .postprocess import match_scene_frames as _match
+    return _match(*args, **kwargs)
+
+
+def grade_precomputed_frames(*args, **kwargs):
+    """The collision check of the recommended placements of candidate frames against the dense scene.  See
+    `postprocess.grade_precomputed_frames`."""
+    from .postprocess import grade_precomputed_frames as _grade
+    return _grade(*args, **kwargs)
+
+
+def label_precomputed_view(*args, **kwargs):
+    """View cloud and `DarbouxScene` in, the curvature model's labels out: `match_scene_frames` and
+    `grade_precomputed_frames` in one call, the view stage of the fast pipeline.  See
+    `postprocess.label_precomputed_view`."""
+    from .postprocess import label_precomputed_view as _label
+    return _label(*args, **kwargs)
+
+
 def best_placement(*args, **kwargs):
     """The baseline data generator's best placement per frame of a `LocalSearch`.  See `postprocess.best_placement`."""
     from .postprocess import best_placement as _best

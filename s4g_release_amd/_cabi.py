@@ -148,6 +148,13 @@ SIGNATURES = {
                                       _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "s4g_contact_select_f32": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _vp, _vp,
                                       _vp, _vp, _vp, _vp]),
+    "s4g_precomputed_select_f32": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64,
+                                          ctypes.c_double, ctypes.c_double, _f32, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                          _vp, _vp, _vp]),
+    "s4g_precomputed_search_workspace_bytes": (_sz, [_i64, _i64, _i64, _i64, _i64]),
+    "s4g_precomputed_search_f32": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64,
+                                          ctypes.POINTER(ctypes.c_float), _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                          _vp, _sz, _vp]),
     "s4g_contact_pairs_workspace_bytes": (_sz, [_i64, _i64]),
     "s4g_contact_pairs_f32": (_int, [_vp, _vp, _vp, _i64, _i64, _i64, ctypes.c_double, ctypes.c_double, _vp, _vp, _vp,
                                      _vp, _vp, _sz, _vp]),

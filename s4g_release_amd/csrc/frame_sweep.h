@@ -106,6 +106,13 @@ __device__ __forceinline__ LocalPoint local_point(const float* __restrict__ g, f
   return l;
 }
 
+// the roll of LOCAL_TO_LOCAL_SEARCH (configs/config.py:79-82): every scan of local_search.hip and of
+// precomputed_view.hip calls this, so they see the same y bit for bit
+__device__ __forceinline__ void ls_roll(float c, float s, float y, float z, float* yy, float* zz) {
+  *yy = c * y + s * z;
+  *zz = (-s) * y + c * z;
+}
+
 // a monotone map float -> int (and back: it is an involution) for every non-NaN value: atomicMax / atomicMin on it give
 // the float maximum / minimum whatever the order of arrival
 __device__ __forceinline__ int f2ord(float f) {
@@ -149,6 +156,43 @@ __global__ __launch_bounds__(256) void compact_valid_kernel(const int* __restric
   }
   for (int f = base + t; f < n; f += 256) valid_index[(size_t)b * n + f] = -1;
   if (t == 0) count[b] = base;
+}
+
+// ---- the normal a view point takes over from its nearest scene point: the rule s4g_contact_select_f32 documents
+// (include/s4g_ops.h), as a function.  scene_normals (3, M) and cloud (3, N) of one scene, i the scene point or < 0,
+// q the view point, cam the camera location.  n = the scene normal of i, or (0, 0, 1) without one; n / |n| in double (a
+// zero normal gives NaN, as numpy does); turned towards the camera as seen from cloud point q; NOT rounded: the caller
+// rounds to fp32 once.  cs_select_kernel (contact_search.hip) holds the same statements inline --------------------------
+struct Normal64 {
+  double x, y, z;
+};
+__device__ __forceinline__ Normal64 scene_normal_towards_camera(const float* __restrict__ scene_normals, int M, int i,
+                                                                const float* __restrict__ cloud, int N, size_t q,
+                                                                const float* __restrict__ cam) {
+  double nx = 0.0, ny = 0.0, nz = 1.0;                 // no neighbour: it must be table
+  if (i >= 0) {
+    const double ax = (double)scene_normals[i], ay = (double)scene_normals[(size_t)M + i],
+                 az = (double)scene_normals[2 * (size_t)M + i];
+    const double len = sqrt(ax * ax + ay * ay + az * az);
+    nx = ax / len; ny = ay / len; nz = az / len;
+  }
+  const double rx = (double)cam[0] - (double)cloud[q], ry = (double)cam[1] - (double)cloud[(size_t)N + q],
+               rz = (double)cam[2] - (double)cloud[2 * (size_t)N + q];
+  if (finite(rx) && finite(ry) && finite(rz)) {       // no reference direction otherwise: n stays
+    if (nx == 0.0 && ny == 0.0 && nz == 0.0) {
+      const double rl = sqrt(rx * rx + ry * ry + rz * rz);
+      if (rl > 0.0) {
+        nx = rx / rl; ny = ry / rl; nz = rz / rl;
+      } else {
+        nz = 1.0;
+      }
+    } else if (nx * rx + ny * ry + nz * rz < 0.0) {
+      nx = -nx; ny = -ny; nz = -nz;
+    }
+  }
+  Normal64 n;
+  n.x = nx; n.y = ny; n.z = nz;
+  return n;
 }
 
 // ---- the gripper box against a cloud: shared by collision_counts_kernel and the frame grading of eval_frames.hip, so

@@ -67,12 +67,6 @@ __device__ __forceinline__ bool ls_gate(const int* __restrict__ a, int slab_n, c
   return a[3] == a[4];                                               // one label (:328)
 }
 
-// the roll of LOCAL_TO_LOCAL_SEARCH (configs/config.py:79-82): both scans call this, so they see the same y bit for bit
-__device__ __forceinline__ void ls_roll(float c, float s, float y, float z, float* yy, float* zz) {
-  *yy = c * y + s * z;
-  *zz = (-s) * y + c * z;
-}
-
 __global__ __launch_bounds__(64) void ls_setup_kernel(
     const float* __restrict__ points, const float* __restrict__ frames, const float* __restrict__ tables, int F,
     LsParams p, const int64_t* __restrict__ frame_count, float* __restrict__ hdr, int* __restrict__ acc,

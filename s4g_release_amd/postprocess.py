@@ -2009,6 +2009,318 @@ def compose_darboux_scene(objects, poses, labels=None):
                         torch.cat(parts["inv_antipodal"]).contiguous())
 
 
+_SCENE_FIELDS = ("points", "normals", "labels", "frames", "inv_frames", "search_score", "inv_search_score",
+                 "antipodal_score", "inv_antipodal_score")
+
+
+@dataclass
+class PrecomputedViewConfig:
+    """The constants of the fast pipeline's view stage (torch_precomputed_single_view_point_cloud.py): the thresholds
+    of `magic_formula` (:181-182), the validity line of `finger_hand` (:384-385), SAMPLE_REGION (None: table_height +
+    SAMPLE_REGION_OFFSET of `search`) and the local search's own constants."""
+    search_threshold: float = 50
+    antipodal_threshold: float = 0.3
+    valid_search_min: float = 1
+    valid_antipodal_min: float = 0.1
+    sample_region: float = None
+    search: LocalSearchConfig = None
+
+    def __post_init__(self):
+        if self.search is None:
+            self.search = LocalSearchConfig()
+
+    @property
+    def region(self):
+        return self.search.table_height + SAMPLE_REGION_OFFSET if self.sample_region is None else self.sample_region
+
+
+@dataclass
+class PrecomputedMatch:
+    """What `match_scene_frames` returns: device tensors, one row per view point.  `nearest` (B, N) int32 the matched
+    scene point or -1, `normals` (B, 3, N) fp32, `flipped` (B, N) bool, `frames` (B, N, 3, 3) fp32, `pre_search`
+    (B, N, L, T) int32, `pre_antipodal` (B, N, L, T) fp32, `mask` (B, N, L, T) bool (`all_frame_bool`), `candidate`
+    (B, N) bool, `frame_index` (B, N) int32 the candidates in ascending order then -1, `frame_count` (B,) int64;
+    `cloud` the noisy view as given."""
+    nearest: torch.Tensor
+    normals: torch.Tensor
+    flipped_i32: torch.Tensor
+    frames: torch.Tensor
+    pre_search: torch.Tensor
+    pre_antipodal: torch.Tensor
+    mask: torch.Tensor
+    candidate_i32: torch.Tensor
+    frame_index: torch.Tensor
+    frame_count: torch.Tensor
+    cloud: torch.Tensor
+    config: PrecomputedViewConfig
+    unbatched: bool = False
+
+    flipped = property(lambda self: self.flipped_i32 != 0)
+    candidate = property(lambda self: self.candidate_i32 != 0)
+
+
+@dataclass
+class PrecomputedSearch:
+    """What `grade_precomputed_frames` returns: device tensors, one row per candidate frame, laid out as `LocalSearch`
+    lays them out (`ints` (B, F, L, T, 6), `scores` (B, F, L, T), `slab_count` (B, F, L), `valid_index` (B, F), `count`
+    (B,)); the named fields are views."""
+    ints: torch.Tensor
+    scores: torch.Tensor
+    slab_count: torch.Tensor
+    valid_i32: torch.Tensor
+    valid_index: torch.Tensor
+    count: torch.Tensor
+    points: torch.Tensor
+    frames: torch.Tensor
+    config: PrecomputedViewConfig
+    unbatched: bool = False
+
+    search_score = property(lambda self: self.ints[..., 0])
+    objects_label = property(lambda self: self.ints[..., 1])
+    back = property(lambda self: self.ints[..., 2])
+    finger = property(lambda self: self.ints[..., 3])
+    close = property(lambda self: self.ints[..., 4])
+    table_collision = property(lambda self: self.ints[..., 5])
+    antipodal_score = property(lambda self: self.scores)
+    valid = property(lambda self: self.valid_i32 != 0)
+
+    def frames_of(self, index=None):
+        """The reference's `valid_frame` (:388-394) of the rows `index` (B, K) (default: `valid_index`): (B, K, L, T, 4,
+        4) = [R | p] @ LOCAL_SEARCH_TO_LOCAL, formed directly as `LocalSearch.frames_of` forms it (no `torch.inverse`,
+        :124).  Rows whose index is -1 are 0."""
+        return LocalSearch.frames_of(self._as_local(), index)
+
+    def _as_local(self):
+        return LocalSearch(self.ints, self.scores, self.slab_count, self.valid_i32, self.valid_index, self.count,
+                           self.points, self.frames, self.config.search, self.unbatched)
+
+
+@dataclass
+class PrecomputedViewLabels:
+    """What `label_precomputed_view` returns: `match` (`PrecomputedMatch`, per view point), `search`
+    (`PrecomputedSearch`, row f = the candidate `match.frame_index[:, f]`) and `cloud_index` (B, F) int32: the view
+    points of the valid frames in ascending order, then -1 -- what the reference's `valid_index` stores (:395)."""
+    match: PrecomputedMatch
+    search: PrecomputedSearch
+    cloud_index: torch.Tensor
+
+    def dump(self, b=0):
+        """The dictionary of the reference's `dump()` (:249-254) for scene b, in the WORLD frame (the camera transform
+        is the caller's, as for `LocalSearch.dump` and `ContactLabels.dump`).  Reads the count on the host."""
+        s = self.search
+        n = int(s.count[b])
+        vi = s.valid_index[b, :n].long()
+        L, T = s.config.search.shape
+        return {"search_score": s.search_score[b, vi].cpu().numpy(),
+                "antipodal_score": s.antipodal_score[b, vi].cpu().numpy(),
+                "objects_label": s.objects_label[b, vi].to(torch.int16).cpu().numpy(),
+                "point_cloud": self.match.cloud[b].cpu().numpy(),
+                "valid_index": self.cloud_index[b, :n].cpu().numpy(),
+                "valid_frame": s.frames_of(s.valid_index[b:b + 1, :n])[0].cpu().numpy()
+                if n else torch.zeros((0, L, T, 4, 4)).numpy()}
+
+
+def _batched_scene(scene):
+    """A `DarbouxScene` (one scene: a leading 1 is added) or any object with its nine fields carrying a leading batch
+    dimension -> dict of contiguous device tensors: points, normals (B, 3, M) fp32, labels (B, M) int32, frames (B, M,
+    3, 3) fp32, the four scores (B, M, L, T)."""
+    got = {}
+    for name in _SCENE_FIELDS:
+        t = getattr(scene, name, None)
+        if not isinstance(t, torch.Tensor) or t.device.type != "cuda":
+            raise RuntimeError("scene.%s must be a CUDA tensor (there is no CPU fallback)" % name)
+        got[name] = t
+    if got["points"].dim() == 2:
+        got = {k: v[None] for k, v in got.items()}
+    pts = got["points"]
+    if pts.dim() != 3 or pts.size(1) != 3 or pts.size(2) < 1:
+        raise RuntimeError("scene.points must be (B, 3, M) with M >= 1")
+    B, _, M = pts.shape
+    ss = got["search_score"]
+    if ss.dim() != 4 or ss.size(0) != B or ss.size(1) != M:
+        raise RuntimeError("scene.search_score must be (B, M, L, T)")
+    L, T = int(ss.size(2)), int(ss.size(3))
+    want = {"points": (B, 3, M), "normals": (B, 3, M), "labels": (B, M), "frames": (B, M, 3, 3),
+            "inv_frames": (B, M, 3, 3)}
+    for name in _SCENE_FIELDS:
+        shape = want.get(name, (B, M, L, T))
+        if tuple(got[name].shape) != shape:
+            raise RuntimeError("scene.%s must be %s, got %s" % (name, shape, tuple(got[name].shape)))
+    if len({t.device for t in got.values()}) != 1:
+        raise RuntimeError("every field of the scene must live on one device")
+    if got["labels"].dtype != torch.int32:
+        raise RuntimeError("scene.labels must be int32, got %s" % got["labels"].dtype)
+    for name in ("search_score", "inv_search_score"):
+        if got[name].dtype != torch.int32:
+            raise RuntimeError("scene.%s must be int32, got %s" % (name, got[name].dtype))
+    out = {k: v.contiguous() for k, v in got.items()}
+    for name in ("points", "normals", "frames", "antipodal_score", "inv_antipodal_score"):
+        out[name] = _F._f32c(out[name], "scene." + name)
+    return out, B, M, L, T
+
+
+def _check_lt(cfg, L, T):
+    cfg.search.check()
+    if not (1 <= L <= LS_MAX_DEPTHS and 1 <= T <= LS_MAX_ANGLES):
+        raise ValueError("need 1..%d depths and 1..%d angles, got %d and %d" % (LS_MAX_DEPTHS, LS_MAX_ANGLES, L, T))
+    if (L, T) != cfg.search.shape:
+        raise ValueError("the scores hold %d x %d placements, config.search %d x %d" % ((L, T) + cfg.search.shape))
+
+
+def match_scene_frames(reference_cloud, cloud, scene, camera, config=None, radius=CURVATURE_RADIUS):
+    """`TorchPrecomputedSingleViewPointCloud._find_match` with `magic_formula` (:130-185) for every view point of every
+    scene in one sync-free, graph-capturable call -> `PrecomputedMatch`.
+
+    reference_cloud (B, 3, N) the noise-free view points the match runs on (`reference_cloud[index_in_ref]`); cloud
+    (B, 3, N) the noisy view; scene a `DarbouxScene` or an object with its nine fields and a leading batch dimension
+    (the scenes of a batch share M; pad with NaN points, which are never a neighbour); camera (B, 3) or (3,) the camera
+    location.  One unbatched view (3, N) gets a leading 1.  Per view point: i = `match_nearest` on reference_cloud; the
+    normal of i, or (0, 0, 1) without one, normalised in double, turned towards the camera seen from the NOISY point,
+    rounded once; flipped where n . frame[:, 0] > 0 in double (:163); the scene frame of i with columns 0 and 1
+    negated where flipped (:166; `inv_frames` is not read); the scene's scores, the inv_* ones where flipped
+    (:167-170); mask = pre_search > search_threshold and pre_antipodal > antipodal_threshold, both compared in double
+    as numpy does (:181-183); a candidate where matched, some mask bit is set and the noisy z > sample_region in fp32
+    (:172-174).  An unmatched or non-finite view point keeps the identity frame and zero scores and is no candidate."""
+    cfg = config or PrecomputedViewConfig()
+    cfg.search.check()
+    for name, t in (("reference_cloud", reference_cloud), ("cloud", cloud), ("camera", camera)):
+        if not isinstance(t, torch.Tensor) or t.device.type != "cuda":
+            raise RuntimeError("%s must be a CUDA tensor (there is no CPU fallback)" % name)
+    sc, B, M, L, T = _batched_scene(scene)
+    _check_lt(cfg, L, T)
+    unbatched = cloud.dim() == 2
+    if unbatched:
+        reference_cloud, cloud = reference_cloud[None], cloud[None]
+    ref = _F._f32c(reference_cloud, "reference_cloud")
+    xyz = _F._f32c(cloud, "cloud")
+    if xyz.dim() != 3 or xyz.size(1) != 3 or xyz.size(0) != B:
+        raise RuntimeError("cloud must be (B, 3, N) with the scene's B")
+    N = xyz.size(2)
+    if tuple(ref.shape) != (B, 3, N):
+        raise RuntimeError("reference_cloud must be (B, 3, N) like cloud")
+    cam = _F._f32c(camera, "camera")
+    if cam.dim() == 1 and cam.numel() == 3:
+        cam = cam.view(1, 3).expand(B, 3)
+    if tuple(cam.shape) != (B, 3):
+        raise RuntimeError("camera must be (B, 3) or (3,)")
+    cam = cam.contiguous()
+    dev = xyz.device
+    if len({ref.device, dev, cam.device, sc["points"].device}) != 1:
+        raise RuntimeError("every input must live on one device")
+    nearest = match_nearest(ref, sc["points"], radius)
+    normals = torch.empty((B, 3, N), dtype=torch.float32, device=dev)
+    flipped = torch.empty((B, N), dtype=torch.int32, device=dev)
+    frames = torch.empty((B, N, 3, 3), dtype=torch.float32, device=dev)
+    pre_search = torch.empty((B, N, L, T), dtype=torch.int32, device=dev)
+    pre_antipodal = torch.empty((B, N, L, T), dtype=torch.float32, device=dev)
+    mask = torch.empty((B, N, L, T), dtype=torch.bool, device=dev)
+    candidate = torch.empty((B, N), dtype=torch.int32, device=dev)
+    frame_index = torch.empty((B, N), dtype=torch.int32, device=dev)
+    frame_count = torch.empty((B,), dtype=torch.int64, device=dev)
+    with torch.cuda.device(dev):
+        rc = _cabi.lib().s4g_precomputed_select_f32(
+            nearest.data_ptr(), xyz.data_ptr(), sc["normals"].data_ptr(), cam.data_ptr(), sc["frames"].data_ptr(),
+            sc["search_score"].data_ptr(), sc["inv_search_score"].data_ptr(), sc["antipodal_score"].data_ptr(),
+            sc["inv_antipodal_score"].data_ptr(), B, N, M, L, T, float(cfg.search_threshold),
+            float(cfg.antipodal_threshold), float(cfg.region), normals.data_ptr(), flipped.data_ptr(),
+            frames.data_ptr(), pre_search.data_ptr(), pre_antipodal.data_ptr(), mask.data_ptr(), candidate.data_ptr(),
+            frame_index.data_ptr(), frame_count.data_ptr(), _F._stream())
+    _cabi.check(rc, "precomputed_select")
+    return PrecomputedMatch(nearest, normals, flipped, frames, pre_search, pre_antipodal, mask, candidate, frame_index,
+                            frame_count, xyz, cfg, unbatched)
+
+
+def grade_precomputed_frames(points, frames, mask, pre_search, pre_antipodal, scene_points, scene_labels, config=None,
+                             frame_count=None):
+    """`TorchPrecomputedSingleViewPointCloud.finger_hand` with `_table_collision_check` (:258-396), which `run_score`
+    (:232-235) loops over the candidate frames, for F rows per scene in one sync-free, graph-capturable call ->
+    `PrecomputedSearch`.
+
+    points (B, F, 3) the noisy view points and frames (B, F, 3, 3) (axes as columns); mask (B, F, L, T) bool,
+    pre_search (B, F, L, T) int32 and pre_antipodal (B, F, L, T) fp32 as `match_scene_frames` gives them; scene_points
+    (B, 3, M) fp32 and scene_labels (B, M) int32 the dense scene (a NaN point is in no region); frame_count (B,) on the
+    device (optional): only the first frame_count[b] rows of scene b are frames.  Unbatched inputs get a leading 1.
+    Only placements whose mask bit is set are collision-checked; one that passes every gate (:327-371) takes over
+    pre_search and pre_antipodal and the close region's label, every other one reads 0 / 0 / no_label.  The only frame
+    gate is mean |frame| < 1e-6 (:295): `grade_local_search`'s reach gate does not exist in this class.  No stale
+    slots, as for `grade_local_search`; `frames_of` is formed directly."""
+    cfg = config or PrecomputedViewConfig()
+    cfg.search.check()
+    for name, t in (("points", points), ("frames", frames), ("mask", mask), ("pre_search", pre_search),
+                    ("pre_antipodal", pre_antipodal), ("scene_labels", scene_labels)):
+        if not isinstance(t, torch.Tensor) or t.device.type != "cuda":
+            raise RuntimeError("%s must be a CUDA tensor (there is no CPU fallback)" % name)
+    unbatched = points.dim() == 2
+    if unbatched:
+        points, frames, mask = points[None], frames[None], mask[None]
+        pre_search, pre_antipodal = pre_search[None], pre_antipodal[None]
+        scene_points, scene_labels = scene_points[None], scene_labels[None]
+    xyz, _, lab, B, M, dev = _dense_scene(scene_points, scene_labels, same_device=[
+        ("points", points), ("frames", frames), ("mask", mask), ("pre_search", pre_search),
+        ("pre_antipodal", pre_antipodal)], size="M", nonempty=True)
+    if mask.dim() != 4 or mask.size(0) != B:
+        raise RuntimeError("mask must be (B, F, L, T)")
+    F, L, T = int(mask.size(1)), int(mask.size(2)), int(mask.size(3))
+    _check_lt(cfg, L, T)
+    if points.dtype != torch.float32 or frames.dtype != torch.float32 or pre_antipodal.dtype != torch.float32:
+        raise RuntimeError("points, frames and pre_antipodal must be float32")
+    if mask.dtype != torch.bool or pre_search.dtype != torch.int32:
+        raise RuntimeError("mask must be bool and pre_search int32")
+    if tuple(points.shape) != (B, F, 3) or tuple(frames.shape) != (B, F, 3, 3):
+        raise RuntimeError("points must be (B, F, 3) and frames (B, F, 3, 3)")
+    if tuple(pre_search.shape) != (B, F, L, T) or tuple(pre_antipodal.shape) != (B, F, L, T):
+        raise RuntimeError("pre_search and pre_antipodal must be (B, F, L, T) like mask")
+    pts, frm, msk = points.contiguous(), frames.contiguous(), mask.contiguous()
+    ps, pa = pre_search.contiguous(), pre_antipodal.contiguous()
+    cnt = _scene_count(frame_count, B, dev, "frame_count")
+    s = cfg.search
+    tb = s.tables()
+    tables = _small_on_device(torch.cat([tb["depth"], tb["lo"], tb["hi"], tb["cos"], tb["sin"]]), torch.float32, dev)
+    ints = torch.empty((B, F, L, T, 6), dtype=torch.int32, device=dev)
+    scores = torch.empty((B, F, L, T), dtype=torch.float32, device=dev)
+    slab = torch.empty((B, F, L), dtype=torch.int32, device=dev)
+    valid = torch.empty((B, F), dtype=torch.int32, device=dev)
+    valid_index = torch.empty((B, F), dtype=torch.int32, device=dev)
+    count = torch.empty((B,), dtype=torch.int64, device=dev)
+    params = (ctypes.c_float * 13)(s.finger_length, s.bottom_length, s.half_hand_thickness, s.half_bottom_width,
+                                   s.half_bottom_space, s.back_collision_margin, s.back_collision_threshold,
+                                   s.finger_collision_threshold, s.close_region_min_points,
+                                   s.table_height + s.table_collision_offset, s.num_points_threshold,
+                                   cfg.valid_search_min, cfg.valid_antipodal_min)
+    ws, nbytes = _workspace(_cabi.lib().s4g_precomputed_search_workspace_bytes(B, M, F, L, T), dev)
+    with torch.cuda.device(dev):
+        rc = _cabi.lib().s4g_precomputed_search_f32(
+            pts.data_ptr(), frm.data_ptr(), msk.data_ptr(), ps.data_ptr(), pa.data_ptr(), xyz.data_ptr(),
+            lab.data_ptr(), B, M, F, L, T, params, int(s.no_label), tables.data_ptr(),
+            None if cnt is None else cnt.data_ptr(), ints.data_ptr(), scores.data_ptr(), slab.data_ptr(),
+            valid.data_ptr(), valid_index.data_ptr(), count.data_ptr(), ws.data_ptr(), nbytes, _F._stream())
+    _cabi.check(rc, "precomputed_search")
+    return PrecomputedSearch(ints, scores, slab, valid, valid_index, count, pts, frm, cfg, unbatched)
+
+
+def label_precomputed_view(reference_cloud, cloud, scene, camera, config=None, radius=CURVATURE_RADIUS):
+    """`TorchPrecomputedSingleViewPointCloud.run_score` (:219-235): view cloud and `DarbouxScene` in, S4G labels out, in
+    one sync-free, graph-capturable call -> `PrecomputedViewLabels`.  `match_scene_frames`, a gather of the candidate
+    rows on the device (F = N rows, `frame_count` of them live, as `label_view` pads), then
+    `grade_precomputed_frames`; see both for the arguments and the decisions.  A view without candidates has
+    `frame_count` 0 (the reference stops in a debugger there)."""
+    cfg = config or PrecomputedViewConfig()
+    m = match_scene_frames(reference_cloud, cloud, scene, camera, cfg, radius)
+    sc = _batched_scene(scene)[0]
+    B, N = m.frame_index.shape
+    L, T = m.mask.shape[2:]
+    g = m.frame_index.clamp(min=0).to(torch.int64)
+    rows = lambda t, width: torch.gather(t.reshape(B, N, width), 1, g.view(B, N, 1).expand(B, N, width))
+    points = rows(m.cloud.transpose(1, 2), 3)
+    frames = rows(m.frames, 9).view(B, N, 3, 3)
+    mask = rows(m.mask, L * T).view(B, N, L, T)
+    pre_search = rows(m.pre_search, L * T).view(B, N, L, T)
+    pre_antipodal = rows(m.pre_antipodal, L * T).view(B, N, L, T)
+    s = grade_precomputed_frames(points, frames, mask, pre_search, pre_antipodal, sc["points"], sc["labels"], cfg,
+                                 m.frame_count)
+    return PrecomputedViewLabels(m, s, map_cloud_index(s.valid_index, m.frame_index))
+
+
 CR_MAX_RESOLUTION = 64                     # the compiled maximum of csrc/close_region.hip
 CR_DEFAULT_POINTS_PER_FRAME = 4096         # the default capacity is F * min(N, this)
 
