@@ -84,7 +84,9 @@ extern "C" {
  *     curvature model's scenes are composed from); s4g_precomputed_select_f32 (every view point's frame, scores and
  *     recommended placements looked up at its nearest point of such a scene) and s4g_precomputed_search_f32 /
  *     s4g_precomputed_search_workspace_bytes (the collision check of the recommended placements against the dense
- *     scene: the view stage of the curvature model's fast label pipeline). */
+ *     scene: the view stage of the curvature model's fast label pipeline);
+ *     s4g_precomputed_baseline_search_f32 / s4g_precomputed_baseline_search_workspace_bytes (the same collision check
+ *     without the label gate and the best-placement fold: the fast baseline labels GPD and PointNetGPD are trained on). */
 #define S4G_ABI_VERSION 14
 
 /* ---------------------------------------------------------------------------
@@ -790,7 +792,8 @@ int s4g_local_search_f32(const float *points_bf3, const float *frames_bf33, cons
 
 /* Baseline inputs (csrc/close_region.hip): TorchBaseLineSingleViewPointCloud.finger_hand's best placement and crop
  * (data_gen/pcd_classes/torch_baseline_single_view_point_cloud.py:220-331), close_region_projection (:334-393) and the
- * crop of torch_precomputed_baseline.py:350-383, without host synchronisation.
+ * crop of torch_precomputed_baseline.py:350-383 (the search of that class is s4g_precomputed_baseline_search_f32
+ * below), without host synchronisation.
  *
  * s4g_best_placement_f32: points (B, F, 3), frames (B, F, 3, 3) (axes as COLUMNS), scores (B, F, L * T) and tables_3l2t
  * as s4g_local_search_f32 reads and writes them.  Per frame, over the L * T placements in flattened order, the first
@@ -1199,6 +1202,42 @@ int s4g_precomputed_search_f32(const float *points_bf3, const float *frames_bf33
                                const int64_t *frame_count_b, int32_t *ints_bfp6, float *scores_bfp, int32_t *slab_bfl,
                                int32_t *valid_bf, int32_t *valid_index_bf, int64_t *count_b, void *workspace,
                                size_t workspace_bytes, s4g_stream_t stream);
+
+/* The fast BASELINE labels (csrc/precomputed_view.hip; added under ABI 14 with no layout change):
+ * TorchPrecomputedBaselinePointCloud.finger_hand with _table_collision_check
+ * (data_gen/pcd_classes/torch_precomputed_baseline.py:227-348, 381-382) for F candidate rows per scene, without host
+ * synchronisation.  Run-to-run bit-identical and batch invariant: integer atomics only, no memset, every launch of the
+ * call is a kernel; graph-capturable.
+ *
+ * Inputs as for s4g_precomputed_search_f32, without pre_search and without labels: points (B, F, 3), frames
+ * (B, F, 3, 3) (axes as COLUMNS), mask bytes (B, F, P) (`all_frame_bool`: pre_antipodal > 0.3 alone, :177-180),
+ * pre_antipodal fp32 (B, F, P), xyz (B, 3, M) fp32, frame_count_b (device, may be NULL).
+ * params11 (HOST pointer) = the first eleven of s4g_precomputed_search_f32's params13; tables_3l2t (DEVICE pointer).
+ * The frame gate, [R^T | -R^T p], the table verdicts, the slab counters, the roll and every region test are those of
+ * s4g_precomputed_search_f32 -- one sweep body compiled twice, here with three accumulator words per placement, no
+ * label read and no atomicMin / atomicMax: back / finger / close / slab are its integers bit for bit.
+ * Gates of a placement in the reference's order: depth without a mask bit (:275), slab >= params[10] (:282), table
+ * verdict clear and mask bit set (:297), back <= params[6] (:312), finger <= params[7] (:323), close >= params[8]
+ * (:333; as written: with params[8] <= 0 an empty close region passes, where s4g_precomputed_search_f32 needs a point
+ * for its label).  There is NO label gate.  A placement that passes reads scores = pre_antipodal, every other one 0.
+ * The fold (:337-348): over the L * T placements in flattened order, depths outer and rolls inner, the first one whose
+ * score is > 0 and > every earlier taken one; a NaN is never taken.  The frame is valid when one was taken (:350);
+ * there is no 1e-4 line as in s4g_best_placement_f32 (with a mask threshold >= 1e-4 the two agree).
+ * Outputs: ints_bfp4 int32 (B, F, P, 4) = {back, finger, close, table_collision}; scores_bfp fp32 (B, F, P);
+ *   slab_bfl int32 (B, F, L); index_bf int32 (B, F) the placement taken or -1; score_bf fp32 (B, F) its score or 0;
+ *   g2l_bf44 fp32 (B, F, 4, 4) = LOCAL_TO_LOCAL_SEARCH[index] @ [R^T | -R^T p] (:381-382), the same fp32 operations as
+ *   s4g_best_placement_f32, all 0 where invalid; valid_index_bf int32 (B, F) ascending, then -1; count_b int64 (B).
+ * Every frame's row holds its own results only (no stale slots).  Limits: those of s4g_precomputed_search_f32.
+ * Workspace: s4g_precomputed_baseline_search_workspace_bytes(B, M, F, L, T) bytes, 256-byte aligned; contents need
+ * not be initialised. */
+size_t s4g_precomputed_baseline_search_workspace_bytes(int64_t B, int64_t M, int64_t F, int64_t L, int64_t T);
+int s4g_precomputed_baseline_search_f32(const float *points_bf3, const float *frames_bf33, const uint8_t *mask_bfp,
+                                        const float *pre_antipodal_bfp, const float *xyz_b3m, int64_t B, int64_t M,
+                                        int64_t F, int64_t L, int64_t T, const float *params11,
+                                        const float *tables_3l2t, const int64_t *frame_count_b, int32_t *ints_bfp4,
+                                        float *scores_bfp, int32_t *slab_bfl, int32_t *index_bf, float *score_bf,
+                                        float *g2l_bf44, int32_t *valid_index_bf, int64_t *count_b, void *workspace,
+                                        size_t workspace_bytes, s4g_stream_t stream);
 
 /* The contact model's per-object frames (csrc/contact_pairs.hip): GenerateContactObjectData of
  * data_gen/data_generator/data_object_contact_point_generator.py for every object of a batch, without host

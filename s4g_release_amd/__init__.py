@@ -137,6 +137,21 @@ def label_baseline_view(*args, **kwargs):
     return _label(*args, **kwargs)
 
 
+def grade_precomputed_baseline_frames(*args, **kwargs):
+    """The fast baseline labels' collision check and best-placement fold of candidate frames against the dense scene.
+    See `postprocess.grade_precomputed_baseline_frames`."""
+    from .postprocess import grade_precomputed_baseline_frames as _grade
+    return _grade(*args, **kwargs)
+
+
+def label_precomputed_baseline_view(*args, **kwargs):
+    """View cloud and `DarbouxScene` in, the inputs of GPD and PointNetGPD out: `match_scene_frames` with the search
+    threshold off, `grade_precomputed_baseline_frames` and `close_regions` of the view in one call.  See
+    `postprocess.label_precomputed_baseline_view`."""
+    from .postprocess import label_precomputed_baseline_view as _label
+    return _label(*args, **kwargs)
+
+
 def score_projections(*args, **kwargs):
     """GPD's grasp logits of the frames of `label_baseline_view`, read from its maps in place.  See
     `postprocess.score_projections`."""

@@ -83,23 +83,7 @@ __global__ __launch_bounds__(256) void cr_best_kernel(
   }
   const float* r = frames + (size_t)row * 9;
   const float px = points[(size_t)row * 3], py = points[(size_t)row * 3 + 1], pz = points[(size_t)row * 3 + 2];
-  float g[3][4];
-#pragma unroll
-  for (int i = 0; i < 3; ++i) {                                                      // [R^T | -R^T p] as ls_setup_kernel forms it
-    const float a = r[i], bb = r[3 + i], c = r[6 + i];
-    g[i][0] = a; g[i][1] = bb; g[i][2] = c;
-    g[i][3] = -__fadd_rn(__fadd_rn(__fmul_rn(a, px), __fmul_rn(bb, py)), __fmul_rn(c, pz));
-  }
-  const int d = bi / T, t = bi % T;
-  const float dl = tables[d], cs = tables[3 * L + t], sn = tables[3 * L + T + t];
-  // LOCAL_TO_LOCAL_SEARCH[i] (config.py:79-89): x - dl, then the roll (y, z) -> (c y + s z, -s y + c z)
-#pragma unroll
-  for (int c = 0; c < 4; ++c) {
-    o[c] = c == 3 ? g[0][3] - dl : g[0][c];
-    o[4 + c] = cs * g[1][c] + sn * g[2][c];
-    o[8 + c] = (-sn) * g[1][c] + cs * g[2][c];
-    o[12 + c] = c == 3 ? 1.f : 0.f;
-  }
+  best_placement_g2l(r, px, py, pz, tables, L, T, bi, o);         // (frame_sweep.h, as text)
 }
 
 // the tables of a pass: rows 0..2 of the frames' matrices

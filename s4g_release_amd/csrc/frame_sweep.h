@@ -113,6 +113,32 @@ __device__ __forceinline__ void ls_roll(float c, float s, float y, float z, floa
   *zz = (-s) * y + c * z;
 }
 
+// LOCAL_TO_LOCAL_SEARCH[bi] @ [R^T | -R^T p] as 16 floats, row-major 4 x 4: the reference's `baseline_frame`
+// (torch_baseline_single_view_point_cloud.py:320-322, torch_precomputed_baseline.py:381-382), formed directly in fp32.
+// r = the frame (axes as columns, row-major 3 x 3), tables = dl[L], lo[L], hi[L], cos[T], sin[T].  cr_best_kernel
+// (close_region.hip) and pvb_finish_kernel (precomputed_view.hip) both call this: the same bits
+__device__ __forceinline__ void best_placement_g2l(const float* __restrict__ r, float px, float py, float pz,
+                                                   const float* __restrict__ tables, int L, int T, int bi,
+                                                   float* __restrict__ o) {
+  float g[3][4];
+#pragma unroll
+  for (int i = 0; i < 3; ++i) {                                                      // [R^T | -R^T p] as ls_setup_kernel forms it
+    const float a = r[i], bb = r[3 + i], c = r[6 + i];
+    g[i][0] = a; g[i][1] = bb; g[i][2] = c;
+    g[i][3] = -__fadd_rn(__fadd_rn(__fmul_rn(a, px), __fmul_rn(bb, py)), __fmul_rn(c, pz));
+  }
+  const int d = bi / T, t = bi % T;
+  const float dl = tables[d], cs = tables[3 * L + t], sn = tables[3 * L + T + t];
+  // LOCAL_TO_LOCAL_SEARCH[i] (config.py:79-89): x - dl, then the roll (y, z) -> (c y + s z, -s y + c z)
+#pragma unroll
+  for (int c = 0; c < 4; ++c) {
+    o[c] = c == 3 ? g[0][3] - dl : g[0][c];
+    o[4 + c] = cs * g[1][c] + sn * g[2][c];
+    o[8 + c] = (-sn) * g[1][c] + cs * g[2][c];
+    o[12 + c] = c == 3 ? 1.f : 0.f;
+  }
+}
+
 // a monotone map float -> int (and back: it is an involution) for every non-NaN value: atomicMax / atomicMin on it give
 // the float maximum / minimum whatever the order of arrival
 __device__ __forceinline__ int f2ord(float f) {

@@ -1,6 +1,7 @@
 // The view stage of the data generator's fast pipeline: TorchPrecomputedSingleViewPointCloud.run_score
 // (data_gen/pcd_classes/torch_precomputed_single_view_point_cloud.py) restated for every view point of every scene.
-// Contract: include/s4g_ops.h (s4g_precomputed_select_f32, s4g_precomputed_search_f32).
+// Contract: include/s4g_ops.h (s4g_precomputed_select_f32, s4g_precomputed_search_f32,
+// s4g_precomputed_baseline_search_f32).
 //
 // s4g_precomputed_select_f32 = _find_match (:130-178) with magic_formula (:180-185) after the nearest-neighbour search
 // (s4g_match_nearest_f32), one thread per view point: the scene normal of its nearest scene point turned towards the
@@ -32,7 +33,17 @@
 // The slab counter of a depth runs when the depth holds a MASK bit (:305), whatever the table says about its rolls, as
 // in the reference: with an all-true mask the slab counts are those of s4g_local_search_f32.
 //
-// Limits: N, M < 2^30, B <= 65 535; for the search F <= 65 535 as well (grid.x of the per-frame kernels).
+// s4g_precomputed_baseline_search_f32 = TorchPrecomputedBaselinePointCloud.finger_hand
+// (data_gen/pcd_classes/torch_precomputed_baseline.py:246-348, 381-382), the baseline variant of the same lookup: the
+// mask is the antipodal threshold alone (the caller's; stage A is s4g_precomputed_select_f32 with the search threshold
+// at -inf), there is NO label gate, and a frame's result is the fold over its passing placements.
+//   pv_setup_kernel<3>   as above, three neutral words per placement
+//   pvb_scan_kernel      the same sweep body (pv_scan, compiled twice), three words: no label is read
+//   pvb_finish_kernel    the gates (:275-333), the looked-up score, the fold (:337-348) by one thread, the matrix (:381)
+//   compact_valid_kernel
+// The crop and maps of the view (:350-380) are s4g_close_region_f32 with x in (0, FINGER_LENGTH).
+//
+// Limits: N, M < 2^30, B <= 65 535; for the searches F <= 65 535 as well (grid.x of the per-frame kernels).
 #include "frame_sweep.h"
 
 namespace s4g {
@@ -51,6 +62,12 @@ constexpr int PV_CHUNK_POINTS = 16384;   // point ranges per scene: ceil(M / 16 
 constexpr int PV_MIN_CHUNKS = 4;
 constexpr int PV_MAX_CHUNKS = 64;
 constexpr int PV_ACC = 5;            // per placement: back, finger, close, label min, label max (ACC_WORDS' prefix)
+// The baseline class (s4g_precomputed_baseline_search_f32) has no label gate: its sweep keeps the three counts only.
+// 20 * 128 * 3 * 4 = 30 KiB of LDS is what 12 five-word slots take, so four workgroups still share a CU and a pass
+// covers 640 frames of a scene instead of 384.  20 is derived from that LDS budget alone: it is not a measured optimum,
+// no other slot count has been timed.
+constexpr int PVB_SLOTS = 20;
+constexpr int PVB_ACC = 3;           // per placement: back, finger, close
 constexpr int PV_HDR = 16;           // per frame: 12 floats of [R^T | -R^T p], the gate verdict, "holds a mask bit", 2 unused
 constexpr unsigned PV_DEPTH_MASKED = 1u << 31;   // in a depth's word: the depth holds a mask bit; bits 0..15 the open rolls
 
@@ -139,6 +156,7 @@ __global__ __launch_bounds__(256) void pv_select_kernel(
 // ---- stage B ----------------------------------------------------------------------------------------------------------
 // words (B, F, L, 2) unsigned: [0] the rolls of the depth that are graded (mask bit set, table verdict clear; bit 31:
 // the depth holds a mask bit at all), [1] the rolls whose box meets the table
+template <int ACC>
 __global__ __launch_bounds__(64) void pv_setup_kernel(
     const float* __restrict__ points, const float* __restrict__ frames, const unsigned char* __restrict__ mask,
     const float* __restrict__ tables, int F, PvParams p, const int64_t* __restrict__ frame_count,
@@ -172,9 +190,9 @@ __global__ __launch_bounds__(64) void pv_setup_kernel(
     const bool mk = ok && mask[row * P + pl] != 0;
     if (ok && hit) atomicOr(&tbl[d], 1u << t);
     if (mk) atomicOr(&opn[d], (hit ? 0u : (1u << t)) | PV_DEPTH_MASKED);
-    int* a = acc + (row * P + pl) * PV_ACC;
+    int* a = acc + (row * P + pl) * ACC;
 #pragma unroll
-    for (int w = 0; w < PV_ACC; ++w) a[w] = acc_neutral(w);
+    for (int w = 0; w < ACC; ++w) a[w] = acc_neutral(w);
   }
   __syncthreads();
   unsigned any = 0u;
@@ -198,28 +216,33 @@ __global__ __launch_bounds__(64) void pv_setup_kernel(
   }
 }
 
-__global__ __launch_bounds__(256) void pv_scan_kernel(
+// The sweep of both searches, written once: LABELS = true is the view stage's five-word form (SLOTS = PV_SLOTS, ACC =
+// PV_ACC), LABELS = false the baseline's three-word form (SLOTS = PVB_SLOTS, ACC = PVB_ACC), which reads no label and
+// does no atomicMin / atomicMax.  Everything else -- the slab counters, the cull, the roll, every comparison -- is the
+// same statement in both, so the counts of the two are the same integers.
+template <bool LABELS, int SLOTS, int ACC>
+__device__ __forceinline__ void pv_scan(
     const float* __restrict__ xyz, const int* __restrict__ labels, const float* __restrict__ hdr,
-    const unsigned* __restrict__ words, const float* __restrict__ tables, int N, int F, PvParams p,
+    const unsigned* __restrict__ words, const float* __restrict__ tables, int N, int F, const PvParams& p,
     int* __restrict__ slab, int* __restrict__ acc, const int64_t* __restrict__ frame_count) {
-  __shared__ float gl[PV_SLOTS][12];
-  __shared__ int live[PV_SLOTS];
+  __shared__ float gl[SLOTS][12];
+  __shared__ int live[SLOTS];
   __shared__ int anylive;
-  __shared__ int scnt[PV_SLOTS][PV_MAX_L];
-  __shared__ unsigned opn[PV_SLOTS][PV_MAX_L];      // per depth, the rolls that are graded; bit 31: the slab is counted
-  __shared__ int cnt[PV_SLOTS][PV_MAX_P][PV_ACC];
+  __shared__ int scnt[SLOTS][PV_MAX_L];
+  __shared__ unsigned opn[SLOTS][PV_MAX_L];         // per depth, the rolls that are graded; bit 31: the slab is counted
+  __shared__ int cnt[SLOTS][PV_MAX_P][ACC];
   __shared__ PvTables tb;
   const int b = blockIdx.z, t = threadIdx.x, lane = t & 63;
   const int L = p.L, T = p.T, P = L * T;
   const float* px = xyz + (size_t)b * 3 * N;
-  const int* lab = labels + (size_t)b * N;
+  const int* lab = LABELS ? labels + (size_t)b * N : nullptr;
   const ChunkRange rg = chunk_range(N);
   if (rg.empty()) return;
   pv_load_tables(tables, L, T, &tb, t);
   const int fmax = frame_rows(frame_count, b, F);
-  for (int j0 = 0; blockIdx.x + PV_GX * j0 < fmax; j0 += PV_SLOTS) {
+  for (int j0 = 0; blockIdx.x + PV_GX * j0 < fmax; j0 += SLOTS) {
     __syncthreads();                                  // (the previous pass's accumulators have been flushed)
-    const int nslot = pass_slots(fmax, PV_GX, j0, PV_SLOTS);
+    const int nslot = pass_slots(fmax, PV_GX, j0, SLOTS);
     if (t == 0) anylive = 0;
     __syncthreads();
     if (t < nslot) {
@@ -234,8 +257,8 @@ __global__ __launch_bounds__(256) void pv_scan_kernel(
       const int sl = i / L, d = i % L;
       opn[sl][d] = words[(((size_t)b * F + blockIdx.x + PV_GX * (j0 + sl)) * L + d) * 2];
     }
-    for (int i = t; i < nslot * P * PV_ACC; i += 256) {
-      ((int*)cnt[i / (P * PV_ACC)])[i % (P * PV_ACC)] = acc_neutral((i % (P * PV_ACC)) % PV_ACC);
+    for (int i = t; i < nslot * P * ACC; i += 256) {
+      ((int*)cnt[i / (P * ACC)])[i % (P * ACC)] = acc_neutral((i % (P * ACC)) % ACC);
     }
     __syncthreads();
     if (!anylive) continue;                           // workgroup-uniform: no cloud read, nothing to flush
@@ -273,7 +296,8 @@ __global__ __launch_bounds__(256) void pv_scan_kernel(
           unsigned rolls = 0;
           for (int d = 0; d < L; ++d) rolls |= ((m[u] >> d) & 1u) ? (opn[sl][d] & 0xffffu) : 0u;
           if (!rolls) continue;
-          const int lb = lab[pt.idx[u]];
+          int lb = 0;
+          if constexpr (LABELS) lb = lab[pt.idx[u]];
           for (int r = 0; r < T; ++r) {
             if (!((rolls >> r) & 1u)) continue;
             float yy, zz;
@@ -289,7 +313,7 @@ __global__ __launch_bounds__(256) void pv_scan_kernel(
               if (fing) atomicAdd(a + 1, 1);
               if (closer) {
                 atomicAdd(a + 2, 1);
-                atomicMin(a + 3, lb); atomicMax(a + 4, lb);
+                if constexpr (LABELS) { atomicMin(a + 3, lb); atomicMax(a + 4, lb); }
               }
             }
           }
@@ -304,15 +328,29 @@ __global__ __launch_bounds__(256) void pv_scan_kernel(
     for (int i = t; i < nslot * P; i += 256) {
       const int sl = i / P, pl = i % P;
       const int* c = cnt[sl][pl];
-      int* a = acc + (((size_t)b * F + blockIdx.x + PV_GX * (j0 + sl)) * P + pl) * PV_ACC;
+      int* a = acc + (((size_t)b * F + blockIdx.x + PV_GX * (j0 + sl)) * P + pl) * ACC;
       if (c[0]) atomicAdd(a + 0, c[0]);
       if (c[1]) atomicAdd(a + 1, c[1]);
       if (c[2]) {
         atomicAdd(a + 2, c[2]);
-        atomicMin(a + 3, c[3]); atomicMax(a + 4, c[4]);
+        if constexpr (LABELS) { atomicMin(a + 3, c[3]); atomicMax(a + 4, c[4]); }
       }
     }
   }
+}
+
+__global__ __launch_bounds__(256) void pv_scan_kernel(
+    const float* __restrict__ xyz, const int* __restrict__ labels, const float* __restrict__ hdr,
+    const unsigned* __restrict__ words, const float* __restrict__ tables, int N, int F, PvParams p,
+    int* __restrict__ slab, int* __restrict__ acc, const int64_t* __restrict__ frame_count) {
+  pv_scan<true, PV_SLOTS, PV_ACC>(xyz, labels, hdr, words, tables, N, F, p, slab, acc, frame_count);
+}
+
+__global__ __launch_bounds__(256) void pvb_scan_kernel(
+    const float* __restrict__ xyz, const float* __restrict__ hdr, const unsigned* __restrict__ words,
+    const float* __restrict__ tables, int N, int F, PvParams p, int* __restrict__ slab, int* __restrict__ acc,
+    const int64_t* __restrict__ frame_count) {
+  pv_scan<false, PVB_SLOTS, PVB_ACC>(xyz, nullptr, hdr, words, tables, N, F, p, slab, acc, frame_count);
 }
 
 // one workgroup per frame, one thread per placement
@@ -361,15 +399,72 @@ __global__ __launch_bounds__(PV_MAX_P) void pv_finish_kernel(
   if (pl == 0) valid[row] = (any_s && any_a) ? 1 : 0;
 }
 
+// The baseline class's finish (torch_precomputed_baseline.py:275-348): one workgroup per frame, one thread per
+// placement for the gates, every comparison as pv_finish_kernel makes it, without the label gate; then ONE thread folds
+// the L * T looked-up scores in flattened order (depths outer, rolls inner) exactly as cr_best_kernel folds them, so the
+// result does not depend on thread arrival.  The frame is valid when a placement was taken (:350): the mask bit already
+// says score > antipodal_threshold, there is no 1e-4 line in this class.
+__global__ __launch_bounds__(PV_MAX_P) void pvb_finish_kernel(
+    const float* __restrict__ points, const float* __restrict__ frames, const float* __restrict__ tables,
+    const float* __restrict__ hdr, const unsigned* __restrict__ words, const int* __restrict__ slab,
+    const int* __restrict__ acc, const float* __restrict__ pre_antipodal, int F, PvParams p, int* __restrict__ ints,
+    float* __restrict__ scores, int* __restrict__ slab_out, int* __restrict__ index, float* __restrict__ best_score,
+    float* __restrict__ g2l) {
+  __shared__ float sc[PV_MAX_P];
+  const int b = blockIdx.y, f = blockIdx.x, pl = threadIdx.x;
+  const int L = p.L, T = p.T, P = L * T;
+  const size_t row = (size_t)b * F + f;
+  const bool ok = ((const int*)(hdr + row * PV_HDR))[12] != 0;      // (0 for padding rows: pv_setup_kernel)
+  if (pl < P) {
+    int vi[4] = {0, 0, 0, 0};
+    float score = 0.f;
+    if (ok) {
+      const int d = pl / T, r = pl % T;
+      const int* a = acc + (row * P + pl) * PVB_ACC;
+      const bool open = (words[(row * L + d) * 2] >> r) & 1u;         // mask bit set and table verdict clear (:275, :297)
+      vi[0] = a[0]; vi[1] = a[1]; vi[2] = a[2];                      // (0 for a placement that was not graded)
+      vi[3] = (words[(row * L + d) * 2 + 1] >> r) & 1u;
+      bool pass = open && !((double)slab[row * L + d] < (double)p.slab_thr);          // :282
+      pass = pass && !((double)a[0] > (double)p.back_thr);            // :312
+      pass = pass && !((double)a[1] > (double)p.fing_thr);            // :323
+      pass = pass && !((double)a[2] < (double)p.min_points);          // :333
+      if (pass) score = pre_antipodal[row * P + pl];                  // :337-338
+    }
+    int* oi = ints + (row * P + pl) * 4;
+#pragma unroll
+    for (int c = 0; c < 4; ++c) oi[c] = vi[c];
+    scores[row * P + pl] = score;
+    sc[pl] = score;
+  }
+  if (pl < L) slab_out[row * L + pl] = ok ? slab[row * L + pl] : 0;
+  __syncthreads();
+  if (pl != 0) return;
+  float best = 0.f;                                                   // the zeroed slot (:119)
+  int bi = -1;
+  for (int i = 0; i < P; ++i) {
+    const float v = sc[i];
+    if (v > best) { best = v; bi = i; }                               // :339; false for a NaN
+  }
+  index[row] = bi;
+  best_score[row] = best;
+  float* o = g2l + row * 16;
+  if (bi < 0) {
+#pragma unroll
+    for (int i = 0; i < 16; ++i) o[i] = 0.f;
+    return;
+  }
+  best_placement_g2l(frames + row * 9, points[row * 3], points[row * 3 + 1], points[row * 3 + 2], tables, L, T, bi, o);
+}
+
 struct PvLayout {
   size_t hdr, acc, slab, words, total;                // byte offsets
 };
-static inline PvLayout pv_layout(size_t B, size_t F, size_t L, size_t T) {
+static inline PvLayout pv_layout(size_t B, size_t F, size_t L, size_t T, size_t acc_words = PV_ACC) {
   const size_t rows = B * F, P = L * T;
   PvLayout o;
   o.hdr = 0;
   o.acc = align256(rows * PV_HDR * sizeof(float));
-  o.slab = o.acc + align256(rows * P * PV_ACC * sizeof(int));
+  o.slab = o.acc + align256(rows * P * acc_words * sizeof(int));
   o.words = o.slab + align256(rows * L * sizeof(int));
   o.total = o.words + align256(rows * L * 2 * sizeof(unsigned));
   return o;
@@ -456,7 +551,7 @@ extern "C" int s4g_precomputed_search_f32(const float* points_bf3, const float* 
   int* slab = (int*)(ws + lay.slab);
   unsigned* words = (unsigned*)(ws + lay.words);
   const dim3 per_frame((unsigned)F, (unsigned)B);
-  hipLaunchKernelGGL(pv_setup_kernel, per_frame, dim3(64), 0, st, points_bf3, frames_bf33,
+  hipLaunchKernelGGL(pv_setup_kernel<PV_ACC>, per_frame, dim3(64), 0, st, points_bf3, frames_bf33,
                      (const unsigned char*)mask_bfp, tables_3l2t, (int)F, p, frame_count_b, hdr, acc, slab, words);
   S4G_LAUNCH_CHECK();
   const dim3 grid(PV_GX, (unsigned)sweep_chunks(M, PV_CHUNK_POINTS, PV_MIN_CHUNKS, PV_MAX_CHUNKS), (unsigned)B);
@@ -468,6 +563,67 @@ extern "C" int s4g_precomputed_search_f32(const float* points_bf3, const float* 
                      (int*)ints_bfp6, scores_bfp, (int*)slab_bfl, (int*)valid_bf);
   S4G_LAUNCH_CHECK();
   hipLaunchKernelGGL(compact_valid_kernel<KeepNonZero>, dim3((unsigned)B), dim3(256), 0, st, (const int*)valid_bf,
+                     (int)F, (int*)valid_index_bf, count_b);
+  S4G_LAUNCH_CHECK();
+  return S4G_OK;
+}
+
+extern "C" size_t s4g_precomputed_baseline_search_workspace_bytes(int64_t B, int64_t M, int64_t F, int64_t L,
+                                                                  int64_t T) {
+  if (B <= 0 || M <= 0 || F <= 0 || L <= 0 || T <= 0 || L > s4g::PV_MAX_L || T > s4g::PV_MAX_T) return 0;
+  return s4g::pv_layout((size_t)B, (size_t)F, (size_t)L, (size_t)T, s4g::PVB_ACC).total;
+}
+
+extern "C" int s4g_precomputed_baseline_search_f32(const float* points_bf3, const float* frames_bf33,
+                                                   const uint8_t* mask_bfp, const float* pre_antipodal_bfp,
+                                                   const float* xyz_b3m, int64_t B, int64_t M, int64_t F, int64_t L,
+                                                   int64_t T, const float* params11, const float* tables_3l2t,
+                                                   const int64_t* frame_count_b, int32_t* ints_bfp4, float* scores_bfp,
+                                                   int32_t* slab_bfl, int32_t* index_bf, float* score_bf,
+                                                   float* g2l_bf44, int32_t* valid_index_bf, int64_t* count_b,
+                                                   void* workspace, size_t workspace_bytes, s4g_stream_t stream) {
+  using namespace s4g;
+  if (B < 0 || M <= 0 || F < 0 || B > 65535 || F > 65535 || M >= (1ll << 30)) return S4G_EINVAL;
+  if (L <= 0 || T <= 0 || L > PV_MAX_L || T > PV_MAX_T) return S4G_EINVAL;
+  if (B * F * L * T > (1ll << 26)) return S4G_EINVAL;       // (the limits of s4g_precomputed_search_f32)
+  if (B == 0) return S4G_OK;
+  if (!count_b) return S4G_EINVAL;
+  hipStream_t st = (hipStream_t)stream;
+  if (F == 0) {
+    hipError_t e = hipMemsetAsync(count_b, 0, (size_t)B * sizeof(int64_t), st);
+    return e == hipSuccess ? S4G_OK : (int)e;
+  }
+  if (!points_bf3 || !frames_bf33 || !mask_bfp || !pre_antipodal_bfp || !xyz_b3m || !params11 || !tables_3l2t ||
+      !ints_bfp4 || !scores_bfp || !slab_bfl || !index_bf || !score_bf || !g2l_bf44 || !valid_index_bf)
+    return S4G_EINVAL;
+  if (!workspace || workspace_bytes < s4g_precomputed_baseline_search_workspace_bytes(B, M, F, L, T))
+    return S4G_EWORKSPACE;
+  PvParams p;
+  p.fl = params11[0]; p.bl = params11[1]; p.hht = params11[2]; p.hbw = params11[3]; p.hbs = params11[4];
+  p.margin = params11[5]; p.back_thr = params11[6]; p.fing_thr = params11[7]; p.min_points = params11[8];
+  p.table_limit = params11[9]; p.slab_thr = params11[10];
+  p.valid_search_min = p.valid_antipodal_min = 0.f;         // (not read: this class has no validity line)
+  p.r2lim = (p.hbw * p.hbw + p.hht * p.hht) * 1.0001f;      // as s4g_precomputed_search_f32
+  p.L = (int)L; p.T = (int)T; p.no_label = 0;
+  const PvLayout lay = pv_layout((size_t)B, (size_t)F, (size_t)L, (size_t)T, PVB_ACC);
+  char* ws = (char*)workspace;
+  float* hdr = (float*)(ws + lay.hdr);
+  int* acc = (int*)(ws + lay.acc);
+  int* slab = (int*)(ws + lay.slab);
+  unsigned* words = (unsigned*)(ws + lay.words);
+  const dim3 per_frame((unsigned)F, (unsigned)B);
+  hipLaunchKernelGGL(pv_setup_kernel<PVB_ACC>, per_frame, dim3(64), 0, st, points_bf3, frames_bf33,
+                     (const unsigned char*)mask_bfp, tables_3l2t, (int)F, p, frame_count_b, hdr, acc, slab, words);
+  S4G_LAUNCH_CHECK();
+  const dim3 grid(PV_GX, (unsigned)sweep_chunks(M, PV_CHUNK_POINTS, PV_MIN_CHUNKS, PV_MAX_CHUNKS), (unsigned)B);
+  hipLaunchKernelGGL(pvb_scan_kernel, grid, dim3(256), 0, st, xyz_b3m, (const float*)hdr, (const unsigned*)words,
+                     tables_3l2t, (int)M, (int)F, p, slab, acc, frame_count_b);
+  S4G_LAUNCH_CHECK();
+  hipLaunchKernelGGL(pvb_finish_kernel, per_frame, dim3(PV_MAX_P), 0, st, points_bf3, frames_bf33, tables_3l2t,
+                     (const float*)hdr, (const unsigned*)words, (const int*)slab, (const int*)acc, pre_antipodal_bfp,
+                     (int)F, p, (int*)ints_bfp4, scores_bfp, (int*)slab_bfl, (int*)index_bf, score_bf, g2l_bf44);
+  S4G_LAUNCH_CHECK();
+  hipLaunchKernelGGL(compact_valid_kernel<KeepNonNegative>, dim3((unsigned)B), dim3(256), 0, st, (const int*)index_bf,
                      (int)F, (int*)valid_index_bf, count_b);
   S4G_LAUNCH_CHECK();
   return S4G_OK;

@@ -2017,7 +2017,9 @@ _SCENE_FIELDS = ("points", "normals", "labels", "frames", "inv_frames", "search_
 class PrecomputedViewConfig:
     """The constants of the fast pipeline's view stage (torch_precomputed_single_view_point_cloud.py): the thresholds
     of `magic_formula` (:181-182), the validity line of `finger_hand` (:384-385), SAMPLE_REGION (None: table_height +
-    SAMPLE_REGION_OFFSET of `search`) and the local search's own constants."""
+    SAMPLE_REGION_OFFSET of `search`) and the local search's own constants.  search_threshold=None switches that
+    threshold off (the mask is the antipodal threshold alone, as `TorchPrecomputedBaselinePointCloud.magic_formula` has
+    it): -inf goes to the kernel, and an int32 score > -inf is true in double."""
     search_threshold: float = 50
     antipodal_threshold: float = 0.3
     valid_search_min: float = 1
@@ -2221,7 +2223,8 @@ def match_scene_frames(reference_cloud, cloud, scene, camera, config=None, radiu
         rc = _cabi.lib().s4g_precomputed_select_f32(
             nearest.data_ptr(), xyz.data_ptr(), sc["normals"].data_ptr(), cam.data_ptr(), sc["frames"].data_ptr(),
             sc["search_score"].data_ptr(), sc["inv_search_score"].data_ptr(), sc["antipodal_score"].data_ptr(),
-            sc["inv_antipodal_score"].data_ptr(), B, N, M, L, T, float(cfg.search_threshold),
+            sc["inv_antipodal_score"].data_ptr(), B, N, M, L, T,
+            float("-inf") if cfg.search_threshold is None else float(cfg.search_threshold),
             float(cfg.antipodal_threshold), float(cfg.region), normals.data_ptr(), flipped.data_ptr(),
             frames.data_ptr(), pre_search.data_ptr(), pre_antipodal.data_ptr(), mask.data_ptr(), candidate.data_ptr(),
             frame_index.data_ptr(), frame_count.data_ptr(), _F._stream())
@@ -2534,8 +2537,8 @@ def label_baseline_view(points, frames, scene_points, scene_normals, cloud=None,
     the label gate, the only difference between the two searches), `best_placement`, then `close_regions` of `cloud` /
     `normals` (default: the scene itself, as in that class) in the best placement of every valid frame.  The
     reference's stop after `grasp_num` valid frames is the caller's slice of `best.valid_index`; no stale slots, as in
-    `grade_local_search`.  `TorchPrecomputedBaselinePointCloud`'s crop and maps are x_range=(0, finger_length) with the
-    view as `cloud`; its lookup of precomputed scene scores stays out of scope.
+    `grade_local_search`.  `TorchPrecomputedBaselinePointCloud`, which looks its scores up in a precomputed scene, is
+    `label_precomputed_baseline_view`.
 
     camera (B, 3) or (3,), the camera location: a cloud without normals gets them from `estimate_normals(cloud,
     camera)` with the reference's radius and max_nn, as that class does for a cloud that has none (:69-70): `cloud`
@@ -2572,18 +2575,204 @@ def label_baseline_view(points, frames, scene_points, scene_normals, cloud=None,
     return BaselineLabels(search, best, regions)
 
 
+@dataclass
+class PrecomputedBaselineConfig:
+    """The constants of the fast baseline labels (torch_precomputed_baseline.py): the threshold of `magic_formula`
+    (:178), SAMPLE_REGION (None: table_height + SAMPLE_REGION_OFFSET of `search`), the local search's own constants and
+    the projection maps'."""
+    antipodal_threshold: float = 0.3
+    sample_region: float = None
+    search: LocalSearchConfig = None
+    projection: ProjectionConfig = None
+
+    def __post_init__(self):
+        if self.search is None:
+            self.search = LocalSearchConfig()
+        if self.projection is None:
+            self.projection = ProjectionConfig()
+
+    def view_config(self):
+        """The `PrecomputedViewConfig` that makes `match_scene_frames` this class's `_find_match`: the search
+        threshold switched off."""
+        return PrecomputedViewConfig(search_threshold=None, antipodal_threshold=self.antipodal_threshold,
+                                     sample_region=self.sample_region, search=self.search)
+
+
+@dataclass
+class PrecomputedBaselineSearch:
+    """What `grade_precomputed_baseline_frames` returns: device tensors, one row per candidate frame.  `ints`
+    (B, F, L, T, 4) int32 = back, finger, close, table verdict; `scores` (B, F, L, T) the looked-up score where every gate
+    passed, else 0; `slab_count` (B, F, L); `points`, `frames` as given; `best` the `BestPlacement` of the fold."""
+    ints: torch.Tensor
+    scores: torch.Tensor
+    slab_count: torch.Tensor
+    points: torch.Tensor
+    frames: torch.Tensor
+    best: BestPlacement
+    config: PrecomputedBaselineConfig
+    unbatched: bool = False
+
+    back = property(lambda self: self.ints[..., 0])
+    finger = property(lambda self: self.ints[..., 1])
+    close = property(lambda self: self.ints[..., 2])
+    table_collision = property(lambda self: self.ints[..., 3])
+    antipodal_score = property(lambda self: self.scores)
+
+
+def grade_precomputed_baseline_frames(points, frames, mask, pre_antipodal, scene_points, config=None, frame_count=None):
+    """`TorchPrecomputedBaselinePointCloud.finger_hand` with `_table_collision_check`
+    (torch_precomputed_baseline.py:227-348, 381-382), which `run_score` (:193-199) loops over the candidate frames, for
+    F rows per scene in one sync-free, graph-capturable call -> `PrecomputedBaselineSearch`.
+
+    points (B, F, 3) the noisy view points and frames (B, F, 3, 3) (axes as columns); mask (B, F, L, T) bool and
+    pre_antipodal (B, F, L, T) fp32 as `match_scene_frames` gives them with the search threshold off; scene_points
+    (B, 3, M) fp32 the dense scene (a NaN point is in no region); frame_count (B,) on the device (optional).  Unbatched
+    inputs get a leading 1.  Only placements whose mask bit is set are collision-checked, with the counts of
+    `grade_precomputed_frames` bit for bit; there is no label gate, so a close region on two objects passes.  `best`
+    is the reference's fold (:337-348): the first placement, depths outer and rolls inner, that passes every gate and
+    whose looked-up score is > 0 and > every earlier taken one; `best.global_to_local` =
+    LOCAL_TO_LOCAL_SEARCH[index] @ [R^T | -R^T p] (:381-382), formed directly.  No stale slots."""
+    cfg = config or PrecomputedBaselineConfig()
+    cfg.search.check()
+    for name, t in (("points", points), ("frames", frames), ("mask", mask), ("pre_antipodal", pre_antipodal),
+                    ("scene_points", scene_points)):
+        if not isinstance(t, torch.Tensor) or t.device.type != "cuda":
+            raise RuntimeError("%s must be a CUDA tensor (there is no CPU fallback)" % name)
+    unbatched = points.dim() == 2
+    if unbatched:
+        points, frames, mask, pre_antipodal = points[None], frames[None], mask[None], pre_antipodal[None]
+        scene_points = scene_points[None]
+    xyz = _F._f32c(scene_points, "scene_points")
+    if xyz.dim() != 3 or xyz.size(1) != 3 or xyz.size(2) < 1:
+        raise RuntimeError("scene_points must be (B, 3, M) with M >= 1")
+    B, _, M = xyz.shape
+    dev = xyz.device
+    if len({dev, points.device, frames.device, mask.device, pre_antipodal.device}) != 1:
+        raise RuntimeError("every input must live on one device")
+    if mask.dim() != 4 or mask.size(0) != B:
+        raise RuntimeError("mask must be (B, F, L, T)")
+    F, L, T = int(mask.size(1)), int(mask.size(2)), int(mask.size(3))
+    _check_lt(cfg, L, T)
+    if points.dtype != torch.float32 or frames.dtype != torch.float32 or pre_antipodal.dtype != torch.float32:
+        raise RuntimeError("points, frames and pre_antipodal must be float32")
+    if mask.dtype != torch.bool:
+        raise RuntimeError("mask must be bool")
+    if tuple(points.shape) != (B, F, 3) or tuple(frames.shape) != (B, F, 3, 3):
+        raise RuntimeError("points must be (B, F, 3) and frames (B, F, 3, 3)")
+    if tuple(pre_antipodal.shape) != (B, F, L, T):
+        raise RuntimeError("pre_antipodal must be (B, F, L, T) like mask")
+    pts, frm, msk, pa = points.contiguous(), frames.contiguous(), mask.contiguous(), pre_antipodal.contiguous()
+    cnt = _scene_count(frame_count, B, dev, "frame_count")
+    s = cfg.search
+    tb = s.tables()
+    tables = _small_on_device(torch.cat([tb["depth"], tb["lo"], tb["hi"], tb["cos"], tb["sin"]]), torch.float32, dev)
+    ints = torch.empty((B, F, L, T, 4), dtype=torch.int32, device=dev)
+    scores = torch.empty((B, F, L, T), dtype=torch.float32, device=dev)
+    slab = torch.empty((B, F, L), dtype=torch.int32, device=dev)
+    index = torch.empty((B, F), dtype=torch.int32, device=dev)
+    score = torch.empty((B, F), dtype=torch.float32, device=dev)
+    g2l = torch.empty((B, F, 4, 4), dtype=torch.float32, device=dev)
+    valid_index = torch.empty((B, F), dtype=torch.int32, device=dev)
+    count = torch.empty((B,), dtype=torch.int64, device=dev)
+    params = (ctypes.c_float * 11)(s.finger_length, s.bottom_length, s.half_hand_thickness, s.half_bottom_width,
+                                   s.half_bottom_space, s.back_collision_margin, s.back_collision_threshold,
+                                   s.finger_collision_threshold, s.close_region_min_points,
+                                   s.table_height + s.table_collision_offset, s.num_points_threshold)
+    ws, nbytes = _workspace(_cabi.lib().s4g_precomputed_baseline_search_workspace_bytes(B, M, F, L, T), dev)
+    with torch.cuda.device(dev):
+        rc = _cabi.lib().s4g_precomputed_baseline_search_f32(
+            pts.data_ptr(), frm.data_ptr(), msk.data_ptr(), pa.data_ptr(), xyz.data_ptr(), B, M, F, L, T, params,
+            tables.data_ptr(), None if cnt is None else cnt.data_ptr(), ints.data_ptr(), scores.data_ptr(),
+            slab.data_ptr(), index.data_ptr(), score.data_ptr(), g2l.data_ptr(), valid_index.data_ptr(),
+            count.data_ptr(), ws.data_ptr(), nbytes, _F._stream())
+    _cabi.check(rc, "precomputed_baseline_search")
+    best = BestPlacement(index, score, g2l, valid_index, count, unbatched)
+    return PrecomputedBaselineSearch(ints, scores, slab, pts, frm, best, cfg, unbatched)
+
+
+@dataclass
+class PrecomputedBaselineLabels:
+    """What `label_precomputed_baseline_view` returns: `match` (`PrecomputedMatch`, per view point), `search`
+    (`PrecomputedBaselineSearch`, row f = the candidate `match.frame_index[:, f]`; `best` = `search.best`), `regions`
+    (`CloseRegions` of the VIEW cloud in the best placement of every valid frame) and `cloud_index` (B, F) int32: the
+    view points of the valid frames in ascending order, then -1 -- what the reference's `valid_index` stores (:377)."""
+    match: PrecomputedMatch
+    search: PrecomputedBaselineSearch
+    regions: CloseRegions
+    cloud_index: torch.Tensor
+
+    best = property(lambda self: self.search.best)
+
+    def dump(self, b=0, grasp_num=None):
+        """The dictionary of the reference's `dump()` (:216-223) for scene b, in the WORLD frame; grasp_num: the
+        reference's stop after that many valid frames.  `baseline_frame` is `se3_inverse(global_to_local)` (local
+        search -> world): the reference stores that matrix times the inverse camera pose, and the camera transform is
+        the caller's, as everywhere else.  `point_cloud` is the whole noisy view (3, N), `valid_index` holds the
+        view-point indices.  Reads the count on the host."""
+        best = self.search.best
+        n = int(best.count[b])
+        if grasp_num is not None:
+            n = min(n, int(grasp_num))
+        vi = best.valid_index[b, :n].long()
+        pts, nrm, maps = self.regions.sets(b, vi.cpu().tolist())
+        return {"antipodal_score": best.score[b, vi].cpu().numpy(),
+                "point_cloud": self.match.cloud[b].cpu().numpy(),
+                "valid_index": self.cloud_index[b, :n].cpu().numpy(),
+                "close_region_points_set": pts, "close_region_normals_set": nrm,
+                "close_region_projection_map_set": maps,
+                "baseline_frame": se3_inverse(best.global_to_local[b, vi]).cpu().numpy()}
+
+
+def label_precomputed_baseline_view(reference_cloud, cloud, scene, camera, config=None, radius=CURVATURE_RADIUS,
+                                    capacity=None):
+    """`TorchPrecomputedBaselinePointCloud.run_score` (torch_precomputed_baseline.py:182-204): view cloud and
+    `DarbouxScene` in, the inputs GPD and PointNetGPD are trained and evaluated on out, in one sync-free,
+    graph-capturable call -> `PrecomputedBaselineLabels`.  `match_scene_frames` with the search threshold off (the
+    mask is pre_antipodal > antipodal_threshold alone, compared in double; the scene's `search_score` fields are carried
+    but not read for the mask), the gather of the candidate rows on the device as `label_precomputed_view` does it,
+    `grade_precomputed_baseline_frames`, then `close_regions` of the VIEW cloud with the matched and oriented normals in
+    the best placement of every valid frame, x in (0, finger_length) (:350-383).  An unmatched or non-finite view point
+    is never a candidate but stays in the crop's cloud with its (0, 0, 1)-towards-camera normal, as the reference has
+    it.  A frame whose best placement has an empty view crop is valid with `regions.count` 0 (the reference appends an
+    empty set).  The reference's stop after `grasp_num` valid frames is the caller's slice of `best.valid_index`; no
+    stale slots; `local_to_global` is never formed by `torch.inverse`."""
+    cfg = config or PrecomputedBaselineConfig()
+    m = match_scene_frames(reference_cloud, cloud, scene, camera, cfg.view_config(), radius)
+    sc = _batched_scene(scene)[0]
+    B, N = m.frame_index.shape
+    L, T = m.mask.shape[2:]
+    g = m.frame_index.clamp(min=0).to(torch.int64)
+    rows = lambda t, width: torch.gather(t.reshape(B, N, width), 1, g.view(B, N, 1).expand(B, N, width))
+    points = rows(m.cloud.transpose(1, 2), 3)
+    frames = rows(m.frames, 9).view(B, N, 3, 3)
+    mask = rows(m.mask, L * T).view(B, N, L, T)
+    pre_antipodal = rows(m.pre_antipodal, L * T).view(B, N, L, T)
+    s = grade_precomputed_baseline_frames(points, frames, mask, pre_antipodal, sc["points"], cfg, m.frame_count)
+    best = s.best
+    s.unbatched = best.unbatched = m.unbatched
+    s4 = cfg.search
+    regions = close_regions(best.global_to_local, m.cloud, m.normals, s4, (0, s4.finger_length), best.index >= 0,
+                            m.frame_count, capacity, cfg.projection)
+    regions.unbatched = m.unbatched
+    return PrecomputedBaselineLabels(m, s, regions, map_cloud_index(best.valid_index, m.frame_index))
+
+
+def _regions_and_best(labels_or_regions, who):
+    if isinstance(labels_or_regions, (BaselineLabels, PrecomputedBaselineLabels)):
+        return labels_or_regions.regions, labels_or_regions.best
+    if isinstance(labels_or_regions, CloseRegions):
+        return labels_or_regions, None
+    raise RuntimeError("%s takes the BaselineLabels of label_baseline_view, the PrecomputedBaselineLabels of "
+                       "label_precomputed_baseline_view or their CloseRegions" % who)
+
+
 def score_projections(labels_or_regions, runner, grasp_num=None):
-    """The GPD baseline's classifier on the maps of `label_baseline_view`, still on the device and without a gathered
+    """The GPD baseline's classifier on the maps of `label_baseline_view` or `label_precomputed_baseline_view`, still on the device and without a gathered
     copy: `runner` (a `baselines.FusedGPD`) reads `regions.maps` in place through
     `best.valid_index[:, :grasp_num]` -> logits (B, K, classes), K = min(grasp_num, F); rows at or past `best.count[b]`
     are zero.  The reference's stop after `grasp_num` valid frames is the slice.  Given `CloseRegions` alone, every
     frame is scored -> (B, F, classes)."""
-    if isinstance(labels_or_regions, BaselineLabels):
-        regions, best = labels_or_regions.regions, labels_or_regions.best
-    elif isinstance(labels_or_regions, CloseRegions):
-        regions, best = labels_or_regions, None
-    else:
-        raise RuntimeError("score_projections takes the BaselineLabels of label_baseline_view or its CloseRegions")
+    regions, best = _regions_and_best(labels_or_regions, "score_projections")
     if not callable(runner):
         raise RuntimeError("runner must be a baselines.FusedGPD")
     if best is None:
@@ -2599,17 +2788,12 @@ def score_projections(labels_or_regions, runner, grasp_num=None):
 
 
 def score_close_regions(labels_or_regions, runner, grasp_num=None):
-    """The PointNetGPD baseline's classifier on the point sets of `label_baseline_view`, still on the device and without
+    """The PointNetGPD baseline's classifier on the point sets of `label_baseline_view` or `label_precomputed_baseline_view`, still on the device and without
     a gathered or sampled copy: `runner` (a `baselines.FusedPointNetGPD`) reads `regions.points` in place through
     `offset` / `count` / `flags` and `best.valid_index[:, :grasp_num]`, every set whole and at its true size -> logits
     (B, K, classes), K = min(grasp_num, F); rows at or past `best.count[b]` are zero, and so is the row of a frame whose
     set is empty or did not fit the capacity.  Given `CloseRegions` alone, every frame is scored -> (B, F, classes)."""
-    if isinstance(labels_or_regions, BaselineLabels):
-        regions, best = labels_or_regions.regions, labels_or_regions.best
-    elif isinstance(labels_or_regions, CloseRegions):
-        regions, best = labels_or_regions, None
-    else:
-        raise RuntimeError("score_close_regions takes the BaselineLabels of label_baseline_view or its CloseRegions")
+    regions, best = _regions_and_best(labels_or_regions, "score_close_regions")
     if not callable(runner):
         raise RuntimeError("runner must be a baselines.FusedPointNetGPD")
     if best is None:
