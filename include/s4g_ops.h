@@ -1384,7 +1384,9 @@ int s4g_darboux_object_grade_f32(const float *xyz_b3n, const float *normals_b3n,
  *   *count (device) their number.
  * s4g_voxel_down_sample_f32: CloudPreProcessor.voxelize (:38-41) = open3d
  *   VoxelDownSample.  origin3 / dims3 are HOST pointers: origin = min(points) -
- *   voxel/2, dims = cells per axis (product < 2^32).  out_3n is (3, N) with row
+ *   voxel/2, dims = cells per axis (product < 2^32); a NaN or infinite origin
+ *   (the bound of a cloud with such a coordinate: crop first) is S4G_EINVAL, as
+ *   are voxel <= 0 and dims <= 0.  out_3n is (3, N) with row
  *   stride N: the first *count columns hold the cell means (double sum in point
  *   order, rounded once), cells in ascending (iz, iy, ix) order.
  * s4g_radius_outlier_mask_f32: CloudPreProcessor.remove_outliers (:31-36) = open3d

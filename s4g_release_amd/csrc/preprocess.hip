@@ -21,6 +21,8 @@
 //             Distances use the library's canonical fp32 arithmetic (s4g_ops.h).
 // All three are HBM-light single-scene passes; the neighbour count reuses the
 // ball query's cell grid (grid.h) with cell edge = radius.
+#include <float.h>
+#include <math.h>
 #include <string.h>
 
 #include "radix_sort.h"
@@ -243,6 +245,9 @@ extern "C" int s4g_voxel_down_sample_f32(const float* xyz_3n, int64_t N, float v
   if (dims3[0] <= 0 || dims3[1] <= 0 || dims3[2] <= 0 ||
       (uint64_t)dims3[0] * (uint64_t)dims3[1] * (uint64_t)dims3[2] >= (1ull << 32))
     return S4G_EINVAL;
+  // a NaN / inf origin (the bound of a cloud with such a coordinate) would clamp a whole axis into one cell
+  for (int a = 0; a < 3; ++a)
+    if (!(fabsf(origin3[a]) <= FLT_MAX)) return S4G_EINVAL;
   hipStream_t st = (hipStream_t)stream;
   if (N == 0) return (int)hipMemsetAsync(count, 0, sizeof(int32_t), st);
   if (!xyz_3n || !out_3n) return S4G_EINVAL;

@@ -53,19 +53,37 @@ def filter_work_space(points, workspace=WORKSPACE):
     return index[:int(count.item())].long()
 
 
+def _voxel_grid(lo, hi, voxel):
+    """(origin (3,) f32, dims (3,) int64) of the voxel grid over the bounds lo / hi (3,): origin = lo - voxel/2,
+    dims = floor((hi - origin) / voxel) + 1, every operation in fp32 (oracle/preprocess.py voxel_grid).  Raises where
+    the kernel would be handed a grid it cannot index: a NaN / inf bound, a dims value >= 2^31 (int32 in the C ABI),
+    2^32 or more cells (uint32 keys)."""
+    v = np.float32(voxel)
+    lo = np.asarray(lo, dtype=np.float32)
+    hi = np.asarray(hi, dtype=np.float32)
+    if not (np.isfinite(lo).all() and np.isfinite(hi).all()):
+        raise RuntimeError("voxel_down_sample: non-finite coordinates in the cloud (NaN or inf), crop first")
+    with np.errstate(over="ignore", invalid="ignore"):
+        origin = (lo - v * np.float32(0.5)).astype(np.float32)
+        top = np.floor(((hi - origin) / v).astype(np.float32))
+    if not (np.isfinite(origin).all() and np.isfinite(top).all()) or (top >= 2.0 ** 31 - 1).any():
+        raise RuntimeError("voxel grid too fine for this cloud (2^31 or more cells on one axis)")
+    dims = top.astype(np.int64) + 1
+    if int(dims[0]) * int(dims[1]) * int(dims[2]) >= 2 ** 32:
+        raise RuntimeError("voxel grid too fine for this cloud (more than 2^32 cells)")
+    return origin, dims
+
+
 def voxel_down_sample(points, voxel_size=VOXEL_SIZE):
-    """(3, V) voxel means (open3d VoxelDownSample semantics, cells in ascending order)."""
+    """(3, V) voxel means (open3d VoxelDownSample semantics, cells in ascending order).  A cloud with a NaN or
+    infinite coordinate has no grid: RuntimeError (crop first, `filter_work_space` drops such points)."""
     p = _cloud(points)
     n = p.size(1)
     if n == 0:
         return p.clone()
     v = np.float32(voxel_size)
-    lo = p.min(dim=1)[0].cpu().numpy()
-    hi = p.max(dim=1)[0].cpu().numpy()
-    origin = (lo - v * np.float32(0.5)).astype(np.float32)
-    dims = (np.floor(((hi - origin) / v).astype(np.float32)).astype(np.int64) + 1)
-    if int(dims[0]) * int(dims[1]) * int(dims[2]) >= 2 ** 32:
-        raise RuntimeError("voxel grid too fine for this cloud (more than 2^32 cells)")
+    # torch's min / max propagate NaN, so one NaN coordinate makes its axis' bounds NaN
+    origin, dims = _voxel_grid(p.min(dim=1)[0].cpu().numpy(), p.max(dim=1)[0].cpu().numpy(), v)
     out = torch.empty((3, n), dtype=torch.float32, device=p.device)
     count = torch.zeros(1, dtype=torch.int32, device=p.device)
     nbytes = _cabi.lib().s4g_voxel_down_sample_workspace_bytes(n)
