@@ -86,7 +86,9 @@ extern "C" {
  *     s4g_precomputed_search_workspace_bytes (the collision check of the recommended placements against the dense
  *     scene: the view stage of the curvature model's fast label pipeline);
  *     s4g_precomputed_baseline_search_f32 / s4g_precomputed_baseline_search_workspace_bytes (the same collision check
- *     without the label gate and the best-placement fold: the fast baseline labels GPD and PointNetGPD are trained on). */
+ *     without the label gate and the best-placement fold: the fast baseline labels GPD and PointNetGPD are trained on);
+ *     s4g_process_views_f32 / s4g_process_views_workspace_bytes (crop, voxel trace and radius-outlier removal of B
+ *     rendered views: the processed cloud and the reference index every view-stage call above starts from). */
 #define S4G_ABI_VERSION 14
 
 /* ---------------------------------------------------------------------------
@@ -1415,6 +1417,30 @@ size_t s4g_radius_outlier_workspace_bytes(int64_t N);
 int s4g_radius_outlier_mask_f32(const float *xyz_3n, int64_t N, float radius,
                                 int32_t nb_points, uint8_t *keep_n, void *ws, size_t ws_bytes,
                                 int flags, s4g_stream_t stream);
+
+/* The view stage's first step for B views in one call (csrc/process_views.hip; added under ABI 14 with no layout
+ * change): `processing_and_trace` of the data generator (data_gen/pcd_classes/
+ * torch_precomputed_single_view_point_cloud.py:64-97) -- workspace crop, open3d's voxel_down_sample_and_trace over the
+ * caller's bounds, remove_radius_outlier, and per kept row its index in the cloud that came in.  No host read; a
+ * captured call is a plain chain of kernel nodes.
+ *   xyz_b3n (B, 3, N) fp32; count_b (B,) int32 on the device or NULL: rows at or past count_b[b] (clamped to [0, N]) do
+ *   not exist.  workspace6 / origin3 / dims3 are HOST pointers as in the three entries above: origin = min_bound -
+ *   voxel / 2, dims = floor((max_bound - origin) / voxel) + 1.  The grid must contain the crop box (the cells of both
+ *   faces of every axis lie in [0, dims - 1]; S4G_EINVAL otherwise): no kept point is clamped.
+ *   Per scene the result equals s4g_crop_indices_f32 -> s4g_voxel_down_sample_f32 (same origin3 / dims3) ->
+ *   s4g_radius_outlier_mask_f32 (same flags) bit for bit:
+ *   points_out_b3n (B, 3, N): the kept voxel means in ascending (iz, iy, ix) cell order, NaN from column count on;
+ *   index_out_bn (B, N) int32: per kept mean the HIGHEST original index among its voxel's points (open3d's trace
+ *   matrix holds the last index added per octant; np.max(trace, axis=1) is the highest of the voxel), -1 from count on;
+ *   counts_out_b3 (B, 3) int32: rows after the crop, voxels, kept means.
+ * Limits: B <= 65 535, B * N < 2^31, cells < 2^32, 0 < radius < 1e18 (S4G_EINVAL).  Workspace:
+ * s4g_process_views_workspace_bytes(B, N) bytes (S4G_EWORKSPACE below that), 256-byte aligned; contents undefined
+ * between calls.  Every refusal happens before the first launch. */
+size_t s4g_process_views_workspace_bytes(int64_t B, int64_t N);
+int s4g_process_views_f32(const float *xyz_b3n, const int32_t *count_b /* may be NULL */, int64_t B, int64_t N,
+                          const float *workspace6, float voxel, const float *origin3, const int32_t *dims3,
+                          float radius, int32_t nb_points, float *points_out_b3n, int32_t *index_out_bn,
+                          int32_t *counts_out_b3, void *ws, size_t ws_bytes, int flags, s4g_stream_t stream);
 
 /* ---------------------------------------------------------------------------
  * The operators in DOUBLE (ABI >= 8).  The reference's extension dispatches every kernel over float and

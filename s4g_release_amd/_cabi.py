@@ -184,6 +184,10 @@ SIGNATURES = {
                                          ctypes.POINTER(ctypes.c_int32), _vp, _vp, _vp, _sz, _vp]),
     "s4g_radius_outlier_workspace_bytes": (_sz, [_i64]),
     "s4g_radius_outlier_mask_f32": (_int, [_vp, _i64, _f32, _i32, _vp, _vp, _sz, _int, _vp]),
+    "s4g_process_views_workspace_bytes": (_sz, [_i64, _i64]),
+    "s4g_process_views_f32": (_int, [_vp, _vp, _i64, _i64, ctypes.POINTER(ctypes.c_float), _f32,
+                                     ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_int32), _f32, _i32, _vp,
+                                     _vp, _vp, _vp, _sz, _int, _vp]),
     "s4g_abi_version": (_int, []),
     "s4g_error_string": (ctypes.c_char_p, [_int]),
     "s4g_workspace_bytes": (_sz, [_int, _i64, _i64, _i64, _i64]),

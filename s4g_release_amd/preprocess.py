@@ -13,8 +13,12 @@ Differences a maintainer should know:
   * subsampling (`sample_single_cloud`, grasp_detector.py:82-92) is seeded
     (splitmix64-keyed permutation) or, as the reference's comment suggests, FPS.
 Every step is a HIP kernel behind the C ABI (include/s4g_ops.h); there is no CPU path.
+
+`process_views` is the batched, sync-free form of crop -> voxel -> outliers with the data GENERATOR's constants and
+its trace (`processing_and_trace` of data_gen/pcd_classes/): the first stage of the label pipeline in postprocess.py.
 """
 import ctypes
+from dataclasses import dataclass
 
 import numpy as np
 import torch
@@ -114,6 +118,128 @@ def radius_outlier_mask(points, nb_points=NUM_POINTS_THRESHOLD, radius=RADIUS_TH
                                                      _F._DIST_FLAGS, _F._stream())
     _cabi.check(rc, "radius_outlier_mask")
     return keep.bool()
+
+
+@dataclass(frozen=True)
+class ViewProcessingConfig:
+    """The constants of the data generator's `processing_and_trace` (data_gen/configs/config.py: WORKSPACE, VOXEL_SIZE,
+    NUM_POINTS_THRESHOLD, RADIUS_THRESHOLD; the voxel bounds are the literals of the call,
+    data_gen/pcd_classes/torch_precomputed_single_view_point_cloud.py:88-89).  They differ from the inference constants
+    above."""
+    workspace: tuple = (-0.40, 0.40, -0.35, 0.35, 0.749, 1.2)
+    voxel_size: float = 0.005
+    voxel_bounds: tuple = ((-0.5, -0.5, 0.7), (0.5, 0.5, 1.5))
+    nb_points: int = 8
+    radius: float = 0.04
+
+    def grid(self):
+        """(origin (3,) f32, dims (3,) int64) of the voxel grid; ValueError where it does not contain the crop box (the
+        cell of a box face, in the kernel's fp32 arithmetic, outside [0, dims - 1])."""
+        if not float(self.voxel_size) > 0.0:
+            raise ValueError("voxel_size must be positive, got %r" % (self.voxel_size,))
+        v = np.float32(self.voxel_size)
+        try:
+            origin, dims = _voxel_grid(self.voxel_bounds[0], self.voxel_bounds[1], v)
+        except RuntimeError as e:
+            raise ValueError(str(e))
+        box = np.asarray(self.workspace, dtype=np.float32)
+        for a in range(3):
+            lo, hi = box[2 * a], box[2 * a + 1]
+            if not lo < hi:                       # an empty (or NaN) box keeps nothing and asks nothing of the grid
+                continue
+            clo = np.floor(np.float32(np.float32(lo - origin[a]) / v))
+            chi = np.floor(np.float32(np.float32(hi - origin[a]) / v))
+            if not (clo >= 0 and chi <= dims[a] - 1):
+                raise ValueError("voxel_bounds %r do not contain the workspace %r on axis %d"
+                                 % (self.voxel_bounds, self.workspace, a))
+        return origin, dims
+
+
+@dataclass
+class ProcessedViews:
+    """What `process_views` returns: device tensors.  `points` (B, 3, N) fp32 the kept voxel means in ascending
+    (iz, iy, ix) cell order, NaN from column count[b] on; `index_in_ref` (B, N) int32 per kept mean the highest original
+    index among its voxel's points, -1 in the padding; `crop_count`, `voxel_count`, `count` (B,) int32 the rows after the
+    crop, the voxels and the kept means."""
+    points: torch.Tensor
+    index_in_ref: torch.Tensor
+    crop_count: torch.Tensor
+    voxel_count: torch.Tensor
+    count: torch.Tensor
+    unbatched: bool = False
+
+    def trace(self, reference):
+        """reference (B, 3, N) (or (3, N) for one view), the noise-free points of the same pixels -> (B, 3, N):
+        reference[b][:, index_in_ref[b]], NaN in the padding -- `reference_cloud` of the view-stage label calls."""
+        ref = _F._f32c(reference, "reference")
+        if ref.dim() == 2:
+            ref = ref[None]
+        if ref.shape != self.points.shape:
+            raise RuntimeError("reference must be %s, got %s" % (tuple(self.points.shape), tuple(ref.shape)))
+        if ref.device != self.points.device:
+            raise RuntimeError("reference must live on the views' device")
+        idx = self.index_in_ref.long()
+        live = (idx >= 0)[:, None, :]
+        got = torch.gather(ref, 2, idx.clamp_(min=0)[:, None, :].expand(-1, 3, -1))
+        return torch.where(live, got, torch.full_like(got, float("nan")))
+
+
+def process_views(clouds, count=None, config=None):
+    """The data generator's `processing_and_trace` (data_gen/pcd_classes/torch_precomputed_single_view_point_cloud.py:
+    64-97; the same code in torch_contact_single_view_point_cloud.py:79-112 and torch_precomputed_baseline.py:76-109)
+    for B rendered views in one sync-free, graph-capturable call -> `ProcessedViews`.
+
+    clouds (B, 3, N) fp32 (one view may be passed as (3, N) and gets a leading 1); count (B,) int32 on the device
+    (optional): the rows of view b at or past count[b] (clamped to [0, N]) do not exist; config a
+    `ViewProcessingConfig` (default: the data generator's constants).  Per view: the crop (`filter_work_space`), the
+    voxel means over the grid of config.voxel_bounds (`voxel_down_sample`'s cells and means, cells ascending), the
+    radius-outlier filter on those means (`radius_outlier_mask`, the distance mode of `functions.set_distance_mode`) --
+    bit for bit what the three single-cloud functions give one after the other -- and `index_in_ref`, the reference's
+    `arange(n)[valid][max(trace, axis=1)][valid3]`.  The voxel bounds must contain the workspace (ValueError): that
+    is what makes the grid, the sort width and the launch chain independent of the data."""
+    if not isinstance(clouds, torch.Tensor) or clouds.device.type != "cuda":
+        raise RuntimeError("clouds must be a CUDA tensor (there is no CPU fallback)")
+    if count is not None and (not isinstance(count, torch.Tensor) or count.device.type != "cuda"):
+        raise RuntimeError("count must be a CUDA tensor (there is no CPU fallback)")
+    cfg = ViewProcessingConfig() if config is None else config
+    unbatched = clouds.dim() == 2
+    if unbatched:
+        clouds = clouds[None]
+    xyz = _F._f32c(clouds, "clouds")
+    if xyz.dim() != 3 or xyz.size(1) != 3:
+        raise RuntimeError("clouds must be (B, 3, N)")
+    B, _, N = xyz.shape
+    if B > 65535 or B * N >= 2 ** 31:
+        raise ValueError("process_views serves B <= 65535 views and B * N < 2^31 rows, got B = %d, N = %d" % (B, N))
+    if not (0.0 < float(cfg.radius) < 1e18) or int(cfg.nb_points) < 0:
+        raise ValueError("radius must be in (0, 1e18) and nb_points >= 0")
+    origin, dims = cfg.grid()
+    live = None
+    if count is not None:
+        if count.dtype != torch.int32:
+            raise RuntimeError("count must be int32, got %s" % count.dtype)
+        if tuple(count.shape) != (B,):
+            raise RuntimeError("count must be (B,)")
+        if count.device != xyz.device:
+            raise RuntimeError("clouds and count must live on one device")
+        live = count.contiguous()
+    dev = xyz.device
+    points = torch.empty((B, 3, N), dtype=torch.float32, device=dev)
+    index = torch.empty((B, N), dtype=torch.int32, device=dev)
+    counts = torch.empty((B, 3), dtype=torch.int32, device=dev)
+    nbytes = _cabi.lib().s4g_process_views_workspace_bytes(B, N)
+    ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
+    box = (ctypes.c_float * 6)(*[float(v) for v in cfg.workspace])
+    o3 = (ctypes.c_float * 3)(*[float(x) for x in origin])
+    d3 = (ctypes.c_int32 * 3)(*[int(x) for x in dims])
+    with torch.cuda.device(dev):
+        rc = _cabi.lib().s4g_process_views_f32(xyz.data_ptr(), None if live is None else live.data_ptr(), B, N, box,
+                                               float(np.float32(cfg.voxel_size)), o3, d3, float(cfg.radius),
+                                               int(cfg.nb_points), points.data_ptr(), index.data_ptr(),
+                                               counts.data_ptr(), ws.data_ptr(), nbytes, _F._DIST_FLAGS, _F._stream())
+    _cabi.check(rc, "process_views")
+    per = counts.t().contiguous()
+    return ProcessedViews(points, index, per[0], per[1], per[2], unbatched)
 
 
 def _splitmix64(x):
