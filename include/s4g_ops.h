@@ -88,7 +88,10 @@ extern "C" {
  *     s4g_precomputed_baseline_search_f32 / s4g_precomputed_baseline_search_workspace_bytes (the same collision check
  *     without the label gate and the best-placement fold: the fast baseline labels GPD and PointNetGPD are trained on);
  *     s4g_process_views_f32 / s4g_process_views_workspace_bytes (crop, voxel trace and radius-outlier removal of B
- *     rendered views: the processed cloud and the reference index every view-stage call above starts from). */
+ *     rendered views: the processed cloud and the reference index every view-stage call above starts from);
+ *     s4g_eval_view_search_f32 / s4g_eval_view_search_workspace_bytes (the first collision-free placement of every
+ *     frame of a view against the view itself) and s4g_eval_scene_grade_f32 / s4g_eval_scene_grade_workspace_bytes
+ *     (its ground truth against the dense labelled scene: the data GPD and PointNetGPD are evaluated on). */
 #define S4G_ABI_VERSION 14
 
 /* ---------------------------------------------------------------------------
@@ -1240,6 +1243,72 @@ int s4g_precomputed_baseline_search_f32(const float *points_bf3, const float *fr
                                         float *scores_bfp, int32_t *slab_bfl, int32_t *index_bf, float *score_bf,
                                         float *g2l_bf44, int32_t *valid_index_bf, int64_t *count_b, void *workspace,
                                         size_t workspace_bytes, s4g_stream_t stream);
+
+/* The baselines' EVALUATION data (csrc/eval_data.hip; added under ABI 14 with no layout change):
+ * EvalDataGenerator.run_collision (data_gen/eval/evaluation_data_generator.py) -- the candidate grasps found on a
+ * rendered view alone, and the ground truth of each against the dense labelled scene -- without host synchronisation.
+ * Both entry points are run-to-run bit-identical and batch invariant (integer atomics and fixed-order sums only),
+ * graph-capturable, with no memset and no host read: every launch of a call is a kernel.
+ *
+ * s4g_eval_view_search_f32 = finger_hand_view (:228-330) with _table_collision_check (:209-226) for F frames of each of
+ * B views.  points (B, F, 3), frames (B, F, 3, 3) (axes as COLUMNS), xyz (B, 3, N) fp32 the VIEW cloud itself,
+ * frame_count_b (device, may be NULL), live_bf (device int32, may be NULL; 0 = the row is not scanned).
+ * params12 (HOST pointer) = the eleven of s4g_precomputed_baseline_search_f32, then TABLE_HEIGHT;
+ * tables_3l2t (DEVICE pointer) as for s4g_local_search_f32.
+ * Per frame: the frame gate mean |frame| < 1e-6 (:242), the reach gate p.z + frame[2, 0] * FINGER_LENGTH < TABLE_HEIGHT
+ * in fp32 (:244, the one s4g_local_search_f32 has and the precomputed classes lack), [R^T | -R^T p] and the table
+ * verdicts as s4g_precomputed_baseline_search_f32 forms them.  The cloud sweep is that entry point's three-word sweep
+ * body compiled again (csrc/pv_sweep.h) with every placement open: there is no mask and no looked-up score, and with
+ * an all-true mask there back / finger / close / slab are the same integers bit for bit.
+ * Gates of a placement, depths outer and rolls inner: slab >= params[10] (:258, a depth below it is skipped whole),
+ * table verdict clear (:273), back <= params[6] (:287), finger <= params[7] (:298), close >= params[8] (:306).  The
+ * FIRST placement that passes is taken (:322-330); there is no score, no label gate and no fold.
+ * Outputs: ints_bfp4 int32 (B, F, P, 4) = {back, finger, close, table_collision}; slab_bfl int32 (B, F, L); index_bf
+ *   int32 (B, F) the placement taken or -1; g2l_bf44 fp32 (B, F, 4, 4) = LOCAL_TO_LOCAL_SEARCH[index] @ [R^T | -R^T p]
+ *   (:322-324) by the fp32 operations of s4g_best_placement_f32, all 0 where invalid; flags_bf int32 (B, F): 1 = not
+ *   scanned (past frame_count_b or live == 0), 2 = the frame or its origin is not finite, 4 = frame gate, 8 = reach
+ *   gate, 0 = searched; valid_index_bf int32 (B, F) ascending, then -1; count_b int64 (B).
+ * A row that is not searched reads 0 / -1 everywhere.  A cloud point that is not finite is in no region.
+ * Limits: those of s4g_precomputed_baseline_search_f32.  F == 0 sets count_b to 0 (by a kernel).
+ * Workspace: s4g_eval_view_search_workspace_bytes(B, N, F, L, T), 256-byte aligned; contents need not be initialised.
+ *
+ * s4g_eval_scene_grade_f32 = finger_hand_scene (:332-391) with _antipodal_score (:161-186) for K poses of each of B
+ * scenes.  g2l (B, K, 4, 4) fp32 global -> gripper (`baseline_frame`), xyz, normals (B, 3, M) fp32, labels (B, M)
+ * int32, pose_count_b (device, may be NULL), live_bk (device int32, may be NULL; 0 = the row is not scanned).
+ * params11 (HOST pointer) = the ten of s4g_eval_frames_f32, then NUM_POINTS_THRESHOLD.
+ * local = g2l @ [p; 1], the region tests, the label test (minimum != maximum), the y extrema, the band rule and the
+ * fixed-order band sums are those of s4g_eval_frames_f32 -- one body compiled twice (csrc/eval_sweep.h): back, finger,
+ * close, the multi-label flag, the bands and the score are its bits wherever both reach the score.  Added: slab =
+ * count(-BOTTOM_LENGTH < lx < FINGER_LENGTH), and this class's order of returns, reported as `stage`:
+ *   1 slab < params[10] (:346); 2 back > params[6] (:360); 3 finger > params[7] (:371); 4 more than one distinct label
+ *   in the close region (:381); 5 close < params[8] (:388); 0 scored (:391).
+ *   non_collision = 0 at stages 1..3, else 1; single_label = 1 at stages 5 and 0, else 0 -- so an EMPTY close region has
+ *   a single label, as written; the score is 0 unless stage is 0 (an empty region never reaches the score).
+ * Outputs: ints_bk8 int32 (B, K, 8) = {slab, back, finger, close, distinct labels > 1, n_left, n_right, stage}, the four
+ *   counts whatever the stage; non_collision_bk, single_label_bk uint8 (B, K); score_bk fp32 (B, K), NaN where a band is
+ *   empty, as s4g_eval_frames_f32; floats_bk4 fp32 (B, K, 4) = {left_y, right_y, mean_left, mean_right}.
+ * A row that is not scanned reads 0 everywhere.  A pose that is not finite is in no region: both booleans 0 and 16 is
+ * added to its stage word.  Limits: those of s4g_eval_frames_f32.
+ * Workspace: s4g_eval_scene_grade_workspace_bytes(B, M, K), 256-byte aligned; contents need not be initialised.
+ *
+ * Decisions of the pair (INTEGRATION.md has them at length).  (1) No stale slots.  (2) `frame` of the reference's dump
+ * is the rigid inverse formed directly by the caller, not torch.inverse.  (3) A frame below the neighbour minimum is
+ * not a candidate: this class's zero frame, which the caller expresses with live_bf.  (4) The eigenvector sign is that
+ * of s4g_darboux_frames_f32.  (5) An empty close region has a single label.  (6) The crop of the view's close region
+ * (s4g_close_region_f32) tests the composed g2l where the reference tests the unshifted slab. */
+size_t s4g_eval_view_search_workspace_bytes(int64_t B, int64_t N, int64_t F, int64_t L, int64_t T);
+int s4g_eval_view_search_f32(const float *points_bf3, const float *frames_bf33, const float *xyz_b3n, int64_t B,
+                             int64_t N, int64_t F, int64_t L, int64_t T, const float *params12,
+                             const float *tables_3l2t, const int64_t *frame_count_b, const int32_t *live_bf,
+                             int32_t *ints_bfp4, int32_t *slab_bfl, int32_t *index_bf, float *g2l_bf44,
+                             int32_t *flags_bf, int32_t *valid_index_bf, int64_t *count_b, void *workspace,
+                             size_t workspace_bytes, s4g_stream_t stream);
+size_t s4g_eval_scene_grade_workspace_bytes(int64_t B, int64_t M, int64_t K);
+int s4g_eval_scene_grade_f32(const float *g2l_bk44, const float *xyz_b3m, const float *normals_b3m,
+                             const int32_t *labels_bm, int64_t B, int64_t M, int64_t K, const float *params11,
+                             const int64_t *pose_count_b, const int32_t *live_bk, int32_t *ints_bk8,
+                             uint8_t *non_collision_bk, uint8_t *single_label_bk, float *score_bk, float *floats_bk4,
+                             void *workspace, size_t workspace_bytes, s4g_stream_t stream);
 
 /* The contact model's per-object frames (csrc/contact_pairs.hip): GenerateContactObjectData of
  * data_gen/data_generator/data_object_contact_point_generator.py for every object of a batch, without host

@@ -152,6 +152,28 @@ def label_precomputed_baseline_view(*args, **kwargs):
     return _label(*args, **kwargs)
 
 
+def grade_eval_view_frames(*args, **kwargs):
+    """The evaluation data's view search: per frame the first collision-free placement against the view cloud itself.
+    See `postprocess.grade_eval_view_frames`."""
+    from .postprocess import grade_eval_view_frames as _grade
+    return _grade(*args, **kwargs)
+
+
+def grade_eval_scene_frames(*args, **kwargs):
+    """The evaluation data's ground truth: collision, single-label and antipodal score of poses against the dense
+    labelled scene.  See `postprocess.grade_eval_scene_frames`."""
+    from .postprocess import grade_eval_scene_frames as _grade
+    return _grade(*args, **kwargs)
+
+
+def label_eval_view(*args, **kwargs):
+    """Rendered view and dense labelled scene in, the baselines' candidate grasps, classifier inputs and ground truth
+    out: `estimate_frames`, `grade_eval_view_frames`, `close_regions` and `grade_eval_scene_frames` in one call.  See
+    `postprocess.label_eval_view`."""
+    from .postprocess import label_eval_view as _label
+    return _label(*args, **kwargs)
+
+
 def score_projections(*args, **kwargs):
     """GPD's grasp logits of the frames of `label_baseline_view`, read from its maps in place.  See
     `postprocess.score_projections`."""

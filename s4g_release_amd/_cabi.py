@@ -159,6 +159,12 @@ SIGNATURES = {
     "s4g_precomputed_baseline_search_f32": (_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64,
                                                    ctypes.POINTER(ctypes.c_float), _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                                    _vp, _vp, _vp, _vp, _sz, _vp]),
+    "s4g_eval_view_search_workspace_bytes": (_sz, [_i64, _i64, _i64, _i64, _i64]),
+    "s4g_eval_view_search_f32": (_int, [_vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, ctypes.POINTER(ctypes.c_float),
+                                        _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "s4g_eval_scene_grade_workspace_bytes": (_sz, [_i64, _i64, _i64]),
+    "s4g_eval_scene_grade_f32": (_int, [_vp, _vp, _vp, _vp, _i64, _i64, _i64, ctypes.POINTER(ctypes.c_float), _vp, _vp,
+                                        _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "s4g_contact_pairs_workspace_bytes": (_sz, [_i64, _i64]),
     "s4g_contact_pairs_f32": (_int, [_vp, _vp, _vp, _i64, _i64, _i64, ctypes.c_double, ctypes.c_double, _vp, _vp, _vp,
                                      _vp, _vp, _sz, _vp]),

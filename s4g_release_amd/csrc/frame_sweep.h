@@ -252,7 +252,7 @@ __device__ __forceinline__ void load_g2l(const float* __restrict__ G, int invert
 
 // the regions of view_collision_checker.py:39-60 / eval_point_cloud.py:70-97 for one point; every inequality strict
 struct GripperRegions {
-  bool back, fing, closer;
+  bool back, fing, closer, slab;     // slab: the depth slab alone, -bottom_length < lx < finger_length
   float ly;
 };
 __device__ __forceinline__ GripperRegions gripper_regions(const float* __restrict__ g, float x, float y, float z,
@@ -267,6 +267,7 @@ __device__ __forceinline__ GripperRegions gripper_regions(const float* __restric
   const bool fr = (ly > -p.half_bottom_width) && (ly < -p.half_bottom_space);              // :56-57
   r.fing = close && zin && (fl || fr);                                                      // :59-60
   r.closer = close && zin && (ly < p.half_bottom_space) && (ly > -p.half_bottom_space);    // eval_point_cloud.py:95-97
+  r.slab = close;
   r.ly = ly;
   return r;
 }

@@ -2758,12 +2758,12 @@ def label_precomputed_baseline_view(reference_cloud, cloud, scene, camera, confi
 
 
 def _regions_and_best(labels_or_regions, who):
-    if isinstance(labels_or_regions, (BaselineLabels, PrecomputedBaselineLabels)):
+    if isinstance(labels_or_regions, (BaselineLabels, PrecomputedBaselineLabels, EvalViewLabels)):
         return labels_or_regions.regions, labels_or_regions.best
     if isinstance(labels_or_regions, CloseRegions):
         return labels_or_regions, None
     raise RuntimeError("%s takes the BaselineLabels of label_baseline_view, the PrecomputedBaselineLabels of "
-                       "label_precomputed_baseline_view or their CloseRegions" % who)
+                       "label_precomputed_baseline_view, the EvalViewLabels of label_eval_view or their CloseRegions" % who)
 
 
 def score_projections(labels_or_regions, runner, grasp_num=None):
@@ -2806,3 +2806,294 @@ def score_close_regions(labels_or_regions, runner, grasp_num=None):
             raise ValueError("grasp_num must be >= 0, got %r" % (grasp_num,))
         index = index[:, :int(grasp_num)]
     return runner(regions.points, offset=regions.offset, count=regions.count, flags=regions.flags, index=index)
+
+
+@dataclass
+class EvalDataConfig:
+    """The constants of the baselines' evaluation data (data_gen/eval/evaluation_data_generator.py): the local search's
+    own (`search`), `grasp_num` (:33, :61), the sample region (None: table_height + SAMPLE_REGION_OFFSET - 0.02 of
+    `search`, :59) and the neighbour minimum of a frame (:145)."""
+    search: LocalSearchConfig = None
+    grasp_num: int = 2000
+    sample_region: float = None
+    min_neighbours: int = 5
+
+    def __post_init__(self):
+        if self.search is None:
+            self.search = LocalSearchConfig()
+
+    def region(self):
+        if self.sample_region is not None:
+            return float(self.sample_region)
+        return self.search.table_height + SAMPLE_REGION_OFFSET - 0.02
+
+
+@dataclass
+class EvalViewSearch:
+    """What `grade_eval_view_frames` returns: device tensors, one row per frame.  `ints` (B, F, L, T, 4) int32 = back,
+    finger, close, table verdict; `slab_count` (B, F, L); `index` (B, F) int32 the FIRST passing placement or -1;
+    `global_to_local` (B, F, 4, 4) the reference's `baseline_frame`, 0 where invalid; `flags` (B, F) int32 (1 not
+    scanned, 2 not finite, 4 frame gate, 8 reach gate); `valid_index` (B, F) ascending and -1 padded; `count` (B,)
+    int64; `points`, `frames` as given."""
+    ints: torch.Tensor
+    slab_count: torch.Tensor
+    index: torch.Tensor
+    global_to_local: torch.Tensor
+    flags: torch.Tensor
+    valid_index: torch.Tensor
+    count: torch.Tensor
+    points: torch.Tensor
+    frames: torch.Tensor
+    config: EvalDataConfig
+    unbatched: bool = False
+
+    back = property(lambda self: self.ints[..., 0])
+    finger = property(lambda self: self.ints[..., 1])
+    close = property(lambda self: self.ints[..., 2])
+    table_collision = property(lambda self: self.ints[..., 3])
+    valid = property(lambda self: self.index >= 0)
+
+
+@dataclass
+class EvalSceneGrades:
+    """What `grade_eval_scene_frames` returns: device tensors, one row per pose.  `ints` (B, K, 8) int32 = slab, back,
+    finger, close, more than one label, n_left, n_right, stage; `non_collision`, `single_label` (B, K) uint8, as the
+    reference stores them; `antipodal_score` (B, K) fp32; `floats` (B, K, 4) = left_y, right_y, mean_left, mean_right.
+    `stage` is the line at which the reference returned: 0 scored, 1 slab, 2 back, 3 finger, 4 labels, 5 few points
+    (`ints[..., 7]` holds 16 more for a pose that is not finite: `not_finite`)."""
+    ints: torch.Tensor
+    non_collision: torch.Tensor
+    single_label: torch.Tensor
+    antipodal_score: torch.Tensor
+    floats: torch.Tensor
+
+    slab = property(lambda self: self.ints[..., 0])
+    back = property(lambda self: self.ints[..., 1])
+    finger = property(lambda self: self.ints[..., 2])
+    close = property(lambda self: self.ints[..., 3])
+    multi_objects = property(lambda self: self.ints[..., 4] != 0)
+    n_left = property(lambda self: self.ints[..., 5])
+    n_right = property(lambda self: self.ints[..., 6])
+    stage = property(lambda self: self.ints[..., 7] & 15)
+    not_finite = property(lambda self: (self.ints[..., 7] & 16) != 0)
+    left_y = property(lambda self: self.floats[..., 0])
+    right_y = property(lambda self: self.floats[..., 1])
+    mean_left = property(lambda self: self.floats[..., 2])
+    mean_right = property(lambda self: self.floats[..., 3])
+
+
+def _live_rows(live, shape, device, name):
+    """The optional row list `live` (B, rows), any dtype -> int32 on the device (0 = not scanned), or None."""
+    if live is None:
+        return None
+    if not isinstance(live, torch.Tensor) or live.device != device or tuple(live.shape) != tuple(shape):
+        raise RuntimeError("%s must be a %s tensor on the device of the cloud" % (name, tuple(shape)))
+    return (live != 0).to(torch.int32).contiguous()
+
+
+def grade_eval_view_frames(points, frames, cloud, config=None, frame_count=None, live=None):
+    """`EvalDataGenerator.finger_hand_view` with `_table_collision_check` (evaluation_data_generator.py:209-330), which
+    `run_collision` (:199-200) loops over the sampled frames, for F frames of each of B views in one sync-free,
+    graph-capturable call -> `EvalViewSearch`.
+
+    points (B, F, 3) frame origins, frames (B, F, 3, 3) (axes as columns), cloud (B, 3, N) fp32 the VIEW cloud the
+    placements are checked against (a point that is not finite is in no region); unbatched inputs get a leading 1.
+    frame_count (B,) on the device (optional): rows at or past it are not scanned; live (B, F) (optional): rows that read
+    0 are not scanned -- `label_eval_view` passes the frames with enough neighbours, whose frame the reference leaves at
+    zero.  Per frame the frame gate, the reach gate, then depths outer and rolls inner the FIRST placement whose depth
+    slab is populated, whose box clears the table, and whose back, finger and close counts pass; there is no score, no
+    label gate and no best.  The counts are those of `grade_precomputed_baseline_frames` with an all-true mask, bit for
+    bit.  No stale slots: a row that is not taken reads index -1 and a zero matrix."""
+    cfg = config or EvalDataConfig()
+    s = cfg.search
+    s.check()
+    for name, t in (("points", points), ("frames", frames), ("cloud", cloud)):
+        if not isinstance(t, torch.Tensor) or t.device.type != "cuda":
+            raise RuntimeError("%s must be a CUDA tensor (there is no CPU fallback)" % name)
+    unbatched = points.dim() == 2
+    if unbatched:
+        points, frames, cloud = points[None], frames[None], cloud[None]
+        live = None if live is None else live[None]
+    xyz = _F._f32c(cloud, "cloud")
+    if xyz.dim() != 3 or xyz.size(1) != 3 or xyz.size(2) < 1:
+        raise RuntimeError("cloud must be (B, 3, N) with N >= 1")
+    B, _, N = xyz.shape
+    dev = xyz.device
+    if len({dev, points.device, frames.device}) != 1:
+        raise RuntimeError("points, frames and cloud must live on one device")
+    if points.dtype != torch.float32 or frames.dtype != torch.float32:
+        raise RuntimeError("points and frames must be float32")
+    if points.dim() != 3 or points.size(0) != B or points.size(2) != 3:
+        raise RuntimeError("points must be (B, F, 3)")
+    F = points.shape[1]
+    if tuple(frames.shape) != (B, F, 3, 3):
+        raise RuntimeError("frames must be (B, F, 3, 3)")
+    pts, frm = points.contiguous(), frames.contiguous()
+    cnt = _scene_count(frame_count, B, dev, "frame_count")
+    lv = _live_rows(live, (B, F), dev, "live")
+    L, T = s.shape
+    tb = s.tables()
+    tables = _small_on_device(torch.cat([tb["depth"], tb["lo"], tb["hi"], tb["cos"], tb["sin"]]), torch.float32, dev)
+    ints = torch.empty((B, F, L, T, 4), dtype=torch.int32, device=dev)
+    slab = torch.empty((B, F, L), dtype=torch.int32, device=dev)
+    index = torch.empty((B, F), dtype=torch.int32, device=dev)
+    g2l = torch.empty((B, F, 4, 4), dtype=torch.float32, device=dev)
+    flags = torch.empty((B, F), dtype=torch.int32, device=dev)
+    valid_index = torch.empty((B, F), dtype=torch.int32, device=dev)
+    count = torch.empty((B,), dtype=torch.int64, device=dev)
+    params = (ctypes.c_float * 12)(s.finger_length, s.bottom_length, s.half_hand_thickness, s.half_bottom_width,
+                                   s.half_bottom_space, s.back_collision_margin, s.back_collision_threshold,
+                                   s.finger_collision_threshold, s.close_region_min_points,
+                                   s.table_height + s.table_collision_offset, s.num_points_threshold, s.table_height)
+    ws, nbytes = _workspace(_cabi.lib().s4g_eval_view_search_workspace_bytes(B, N, F, L, T), dev)
+    with torch.cuda.device(dev):
+        rc = _cabi.lib().s4g_eval_view_search_f32(
+            pts.data_ptr(), frm.data_ptr(), xyz.data_ptr(), B, N, F, L, T, params, tables.data_ptr(),
+            None if cnt is None else cnt.data_ptr(), None if lv is None else lv.data_ptr(), ints.data_ptr(),
+            slab.data_ptr(), index.data_ptr(), g2l.data_ptr(), flags.data_ptr(), valid_index.data_ptr(),
+            count.data_ptr(), ws.data_ptr(), nbytes, _F._stream())
+    _cabi.check(rc, "eval_view_search")
+    return EvalViewSearch(ints, slab, index, g2l, flags, valid_index, count, pts, frm, cfg, unbatched)
+
+
+def grade_eval_scene_frames(global_to_local, scene_points, scene_normals, scene_labels, config=None, count=None,
+                            live=None):
+    """`EvalDataGenerator.finger_hand_scene` with `_antipodal_score` (evaluation_data_generator.py:161-186,332-391),
+    which `run_collision` (:205-206) loops over the valid grasps, for K poses of each of B scenes in one sync-free,
+    graph-capturable call -> `EvalSceneGrades`.
+
+    global_to_local (B, K, 4, 4) fp32 (`EvalViewSearch.global_to_local`, the reference's `baseline_frame`);
+    scene_points, scene_normals (B, 3, M) fp32; scene_labels (B, M) int32.  count (B,) on the device (optional): rows at
+    or past it are not scanned; live (B, K) (optional): rows that read 0 are not scanned; such rows read 0 everywhere.
+    The transform, the regions, the label test, the bands and the score are `eval_frames`' bit for bit wherever both
+    reach the score; this class adds the slab count and returns in its own order (`stage`).  An EMPTY close region has
+    a single label, as written."""
+    cfg = config or EvalDataConfig()
+    s = cfg.search
+    if not isinstance(global_to_local, torch.Tensor) or global_to_local.device.type != "cuda":
+        raise RuntimeError("global_to_local must be a CUDA tensor (there is no CPU fallback)")
+    if global_to_local.dtype != torch.float32:
+        raise RuntimeError("global_to_local must be float32")
+    if global_to_local.dim() == 3:
+        global_to_local = global_to_local[None]
+        scene_points, scene_normals, scene_labels = scene_points[None], scene_normals[None], scene_labels[None]
+        live = None if live is None else live[None]
+    xyz, nrm, lab, B, M, dev = _dense_scene(scene_points, scene_labels, scene_normals,
+                                            [("global_to_local", global_to_local)], size="M", nonempty=True)
+    if global_to_local.dim() != 4 or global_to_local.size(0) != B or tuple(global_to_local.shape[2:]) != (4, 4):
+        raise RuntimeError("global_to_local must be (B, K, 4, 4)")
+    K = global_to_local.shape[1]
+    g2l = global_to_local.contiguous()
+    cnt = _scene_count(count, B, dev, "count")
+    lv = _live_rows(live, (B, K), dev, "live")
+    ints = torch.empty((B, K, 8), dtype=torch.int32, device=dev)
+    non_collision = torch.empty((B, K), dtype=torch.uint8, device=dev)
+    single_label = torch.empty((B, K), dtype=torch.uint8, device=dev)
+    score = torch.empty((B, K), dtype=torch.float32, device=dev)
+    floats = torch.empty((B, K, 4), dtype=torch.float32, device=dev)
+    params = (ctypes.c_float * 11)(s.finger_length, s.bottom_length, s.half_hand_thickness, s.half_bottom_width,
+                                   s.half_bottom_space, s.back_collision_margin, s.back_collision_threshold,
+                                   s.finger_collision_threshold, s.close_region_min_points, s.neighbor_depth,
+                                   s.num_points_threshold)
+    ws, nbytes = _workspace(_cabi.lib().s4g_eval_scene_grade_workspace_bytes(B, M, K), dev)
+    with torch.cuda.device(dev):
+        rc = _cabi.lib().s4g_eval_scene_grade_f32(
+            g2l.data_ptr(), xyz.data_ptr(), nrm.data_ptr(), lab.data_ptr(), B, M, K, params,
+            None if cnt is None else cnt.data_ptr(), None if lv is None else lv.data_ptr(), ints.data_ptr(),
+            non_collision.data_ptr(), single_label.data_ptr(), score.data_ptr(), floats.data_ptr(), ws.data_ptr(),
+            nbytes, _F._stream())
+    _cabi.check(rc, "eval_scene_grade")
+    return EvalSceneGrades(ints, non_collision, single_label, score, floats)
+
+
+@dataclass
+class EvalViewLabels:
+    """What `label_eval_view` returns: `frames` (`DarbouxFrames` of the sampled view points), `search`
+    (`EvalViewSearch`, row f = frame f), `regions` (`CloseRegions` of the VIEW cloud in the placement taken) and `truth`
+    (`EvalSceneGrades` of the taken placements against the dense scene; a row without one reads 0).  `cloud`, `normals`
+    are the view as it was searched; the scene tensors are kept for `dump`."""
+    frames: DarbouxFrames
+    search: EvalViewSearch
+    regions: CloseRegions
+    truth: EvalSceneGrades
+    cloud: torch.Tensor
+    normals: torch.Tensor
+    scene_points: torch.Tensor
+    scene_normals: torch.Tensor
+    scene_labels: torch.Tensor
+
+    best = property(lambda self: self.search)     # (what `score_projections` / `score_close_regions` read: valid_index)
+
+    def dump(self, b=0):
+        """The dictionary of the reference's `dump()` (evaluation_data_generator.py:96-107) for view b in the WORLD
+        frame (the camera transform is the caller's), the grasps in the reference's append order, which is ascending
+        frame.  `frame` is `se3_inverse(global_to_local)`, the rigid inverse formed directly where the reference calls
+        `torch.inverse`.  Reads the count on the host."""
+        n = int(self.search.count[b])
+        vi = self.search.valid_index[b, :n].long()
+        pts, nrm, maps = self.regions.sets(b, vi.cpu().tolist())
+        return {"frame": se3_inverse(self.search.global_to_local[b, vi]).cpu().numpy(),
+                "antipodal_score": self.truth.antipodal_score[b, vi].cpu().numpy(),
+                "non_collision_bool": self.truth.non_collision[b, vi].cpu().numpy(),
+                "single_label_bool": self.truth.single_label[b, vi].cpu().numpy(),
+                "view_cloud": self.cloud[b].t().contiguous().cpu().numpy(),
+                "scene_cloud": self.scene_points[b].t().contiguous().cpu().numpy(),
+                "scene_label": self.scene_labels[b].cpu().numpy(),
+                "scene_normal": self.scene_normals[b].t().contiguous().cpu().numpy(),
+                "close_region_points_set": pts, "close_region_normals_set": nrm,
+                "close_region_projection_map_set": maps}
+
+
+def label_eval_view(cloud, normals, scene_points, scene_normals, scene_labels, config=None, frame_index=None,
+                    frame_count=None, camera=None, projection=None, capacity=None, generator=None):
+    """`EvalDataGenerator.run_collision` (data_gen/eval/evaluation_data_generator.py:188-207), what
+    `generate_eval_data.py` runs per rendered view: rendered view and dense labelled scene in, the baselines'
+    candidate grasps with their classifier inputs and their ground truth out, as one sync-free chain ->
+    `EvalViewLabels`.
+
+    cloud (B, 3, N) fp32 the processed view (`process_views`), normals like it or None with `camera` (B, 3) or (3,):
+    `estimate_normals(cloud, camera)` (:65-66).  scene_points, scene_normals (B, 3, M) fp32, scene_labels (B, M) int32.
+    Steps: `estimate_frames` at frame_index; `grade_eval_view_frames` of those frames against the VIEW with live =
+    neighbour count >= config.min_neighbours; `close_regions` of the view in the placement taken, x in (-bottom_length,
+    finger_length) (the depth slab is this class's only x filter); `grade_eval_scene_frames` of the taken placements.
+
+    frame_index (B, F) int32 with frame_count (B,), or None: the first config.grasp_num points with z >
+    config.region() in ascending index (:59-61).  `generator` (a device torch.Generator) shuffles those candidates on
+    the device first, as the reference's `np.random.shuffle` does; its unseeded order cannot be reproduced.
+
+    Decisions.  (1) No stale slots.  (2) `dump()['frame']` is the rigid inverse formed directly.  (3) A point with
+    fewer than min_neighbours neighbours is not a candidate: the reference leaves its frame at zero (:63, :145), which
+    fails the frame gate, where `estimate_frames` returns the identity and reports `count`.  (4) The eigenvector sign
+    is `estimate_frames`' pinned rule; the other sign maps roll theta to -theta and can change which placement is
+    first.  (5) An empty scene close region has a single label, as written.  (6) The crop tests the composed matrix
+    where the reference tests the unshifted slab: points within rounding of a face are ambiguous, as in
+    `label_baseline_view`."""
+    cfg = config or EvalDataConfig()
+    if not isinstance(cloud, torch.Tensor) or cloud.device.type != "cuda":
+        raise RuntimeError("cloud must be a CUDA tensor (there is no CPU fallback)")
+    if cloud.dim() != 3:
+        raise RuntimeError("cloud must be (B, 3, N)")
+    if normals is None:
+        if camera is None:
+            raise RuntimeError("a cloud without normals needs the camera location")
+        normals = estimate_normals(cloud, camera).normals
+    xyz = _F._f32c(cloud, "cloud")
+    B, _, N = xyz.shape
+    if frame_index is None:
+        if frame_count is not None:
+            raise RuntimeError("frame_count needs a frame_index")
+        index, cnt = sample_frame_index(xyz, cfg.region())
+        if generator is not None:
+            keys = torch.rand((B, N), generator=generator, device=xyz.device)
+            pad = torch.arange(N, device=xyz.device).view(1, N) >= cnt.view(B, 1)
+            index = torch.gather(index, 1, torch.argsort(keys.masked_fill(pad, 2.0), dim=1))
+        F = min(int(cfg.grasp_num), N)
+        frame_index, frame_count = index[:, :F].contiguous(), cnt.clamp(max=F)
+    fr = estimate_frames(xyz, normals, frame_index, frame_count, min_neighbours=cfg.min_neighbours)
+    search = grade_eval_view_frames(fr.points, fr.frames, xyz, cfg, fr.frame_count, fr.count >= cfg.min_neighbours)
+    taken = search.index >= 0
+    regions = close_regions(search.global_to_local, xyz, normals.contiguous(), cfg.search, None, taken, fr.frame_count,
+                            capacity, projection)
+    truth = grade_eval_scene_frames(search.global_to_local, scene_points, scene_normals, scene_labels, cfg,
+                                    fr.frame_count, taken)
+    return EvalViewLabels(fr, search, regions, truth, xyz, normals, scene_points, scene_normals, scene_labels)
