@@ -1518,6 +1518,10 @@ int s4g_process_views_f32(const float *xyz_b3n, const int32_t *count_b /* may be
  * types, tie rules and padding as the *_f32 entry points; plain kernels (S4G never uses double).
  *   s4g_fps_f64: ws = (B, N) doubles (the reference's `temp`), ws_bytes >= 8 B N.
  *   s4g_ball_query_f64: `radius` is a C float as in ball_query.h and is cast to double before squaring.
+ *   s4g_three_nn_f64: the reference's initial distance 1e40 is FINITE in double: a slot no key entered reports it
+ *     (not +inf), a key 1e20 or more away enters nowhere, and the initialiser -1 can sit in any of the three slots
+ *     (one or two keys nearer than 1e20): each reports index 0, as every 3-NN entry point does (s4g_three_nn_f32).
+ *   The two backwards refuse a NULL argument before gin is zero-filled.
  *   gather_points = group_points with K == 1.  Inverse-distance weights: torch ops in the caller.
  * ------------------------------------------------------------------------- */
 int s4g_fps_f64(const double *xyz_b3n, int64_t B, int64_t N, int64_t M, int64_t *idx_bm, void *ws,

@@ -154,8 +154,10 @@ __global__ __launch_bounds__(256) void three_nn_f64_kernel(const double* __restr
     }
   }
   const size_t o = ((size_t)b * N1 + i) * 3;
-  // (an unfilled slot -- non-finite query -- as index 0, never the initialiser -1: see three_nn.hip nn_safe_index)
-  idx[o] = i0 < 0 ? 0 : i0; idx[o + 1] = i1; idx[o + 2] = i2;
+  // (an unfilled slot as index 0, never the initialiser -1: see three_nn.hip nn_safe_index.  1e40 is finite in double,
+  // so the first keys nearer than that push (1e40, -1) on to slot 1 and slot 2: a query with one or two such keys
+  // -- the others 1e20 away, or non-finite -- keeps it there, and all three slots need the guard)
+  idx[o] = i0 < 0 ? 0 : i0; idx[o + 1] = i1 < 0 ? 0 : i1; idx[o + 2] = i2 < 0 ? 0 : i2;
   d2[o] = b0; d2[o + 1] = b1; d2[o + 2] = b2;
 }
 
@@ -184,10 +186,11 @@ __global__ __launch_bounds__(256) void interp_f64_kernel(const double* __restric
   const double* __restrict__ row = f + ((size_t)b * C + ch) * N2;
   const size_t o = ((size_t)b * N1 + i) * 3;
   double acc;                                                     // acc = 0; acc += f_k w_k (:160-174)
+  // (the sums start from +0.0 as written there: three products of -0.0 add up to +0.0, not -0.0)
   if constexpr (FMAD) {
-    acc = __fma_rn(row[idx[o + 2]], w[o + 2], __fma_rn(row[idx[o + 1]], w[o + 1], __dmul_rn(row[idx[o]], w[o])));
+    acc = __fma_rn(row[idx[o + 2]], w[o + 2], __fma_rn(row[idx[o + 1]], w[o + 1], __fma_rn(row[idx[o]], w[o], 0.0)));
   } else {
-    acc = __dadd_rn(__dadd_rn(__dmul_rn(row[idx[o]], w[o]), __dmul_rn(row[idx[o + 1]], w[o + 1])),
+    acc = __dadd_rn(__dadd_rn(__dadd_rn(0.0, __dmul_rn(row[idx[o]], w[o])), __dmul_rn(row[idx[o + 1]], w[o + 1])),
                     __dmul_rn(row[idx[o + 2]], w[o + 2]));
   }
   out[((size_t)b * C + ch) * N1 + i] = acc;
@@ -286,13 +289,12 @@ extern "C" int s4g_group_points_backward_f64(const double* gout_bcmk, const int6
                                              int64_t N, int64_t M, int64_t K, double* gin_bcn, s4g_stream_t stream) {
   if (B < 0 || C < 0 || N <= 0 || M < 0 || K < 0 || B > 65535 || C > 65535 || N >= (1ll << 31)) return S4G_EINVAL;
   if (B == 0 || C == 0) return S4G_OK;
-  if (!gin_bcn) return S4G_EINVAL;
+  const int64_t MK = M * K;
+  if (!gin_bcn || (MK != 0 && (!gout_bcmk || !idx_bmk))) return S4G_EINVAL;   // before anything is written
   hipStream_t st = (hipStream_t)stream;
   const hipError_t e = hipMemsetAsync(gin_bcn, 0, sizeof(double) * (size_t)(B * C * N), st);
   if (e != hipSuccess) return (int)e;
-  const int64_t MK = M * K;
   if (MK == 0) return S4G_OK;
-  if (!gout_bcmk || !idx_bmk) return S4G_EINVAL;
   hipLaunchKernelGGL(group_bwd_f64_kernel, dim3((unsigned)((MK + 255) / 256), (unsigned)C, (unsigned)B), dim3(256), 0, st,
                      gout_bcmk, idx_bmk, (int)C, (int)N, MK, gin_bcn);
   S4G_LAUNCH_CHECK();
@@ -321,12 +323,11 @@ extern "C" int s4g_three_interpolate_backward_f64(const double* gout_bcn1, const
                                                   s4g_stream_t stream) {
   if (B < 0 || C < 0 || N2 <= 0 || N1 < 0 || B > 65535 || C > 65535 || N1 >= (1ll << 31)) return S4G_EINVAL;
   if (B == 0 || C == 0) return S4G_OK;
-  if (!gin_bcn2) return S4G_EINVAL;
+  if (!gin_bcn2 || (N1 != 0 && (!gout_bcn1 || !idx_bn3 || !w_bn3))) return S4G_EINVAL;   // before anything is written
   hipStream_t st = (hipStream_t)stream;
   const hipError_t e = hipMemsetAsync(gin_bcn2, 0, sizeof(double) * (size_t)(B * C * N2), st);
   if (e != hipSuccess) return (int)e;
   if (N1 == 0) return S4G_OK;
-  if (!gout_bcn1 || !idx_bn3 || !w_bn3) return S4G_EINVAL;
   hipLaunchKernelGGL(interp_bwd_f64_kernel, dim3((unsigned)((N1 + 255) / 256), (unsigned)C, (unsigned)B), dim3(256), 0, st,
                      gout_bcn1, idx_bn3, w_bn3, (int)C, (int)N2, (int)N1, gin_bcn2);
   S4G_LAUNCH_CHECK();
