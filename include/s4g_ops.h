@@ -59,6 +59,8 @@ extern "C" {
  *     (pose decode for an absolute translation head); no layout change.
  * 14: S4G_GEMM_LOAD_CHANNEL_FIRST, S4G_GEMM_EPI_MAX_CHANNEL_FIRST and s4g_gemm_desc_t.a_L (any SharedMLP / SA max-pool
  *     on its own (B, C, L) tensors: s4g_release_amd.accelerate), s4g_amax_per_scene_f32.
+ *     s4g_gemm_desc_t.cbias (a per-centroid bias of the GATHER_ADD loader: the edge levels of MODEL.TYPE "EDGEPN2D";
+ *     NULL behaves as before the member existed; it sits in front of a_L, whose offset grew by 8).
  *     Added under 14 with no layout change: s4g_eval_frames_f32 / s4g_eval_frames_workspace_bytes (batched antipodal
  *     and collision grading of grasp frames against a labelled scene cloud with normals); s4g_local_search_f32 /
  *     s4g_local_search_workspace_bytes (the data generator's per-frame local grasp search); s4g_darboux_frames_f32 /
@@ -311,7 +313,8 @@ int s4g_interp_weights_f32(const float *d2_bn3, int64_t B, int64_t N1,
  *                                W_feat . features, (B*N, Cf = Cin) channels-last):
  *                                A row p = relu(F[b*N + gidx[p]] + W_xyz . (xyz - ctr) + b1),
  *                                mlp1_w = Cin x (wx, wy, wz, bias); a_amax bounds |F| and
- *                                a_amax_floor the xyz + bias part (the two are ADDED)
+ *                                a_amax_floor the xyz + bias part (the two are ADDED); with `cbias` the
+ *                                bias is a row per centroid (see the member)
  *         S4G_GEMM_LOAD_CHANNEL_FIRST  (ABI >= 14) A is a (B, Cin, a_L) fp32 tensor, channels first:
  *                                A row p = b*a_L + l = A[b][0..Cin)[l]; any Cin >= 1 and any a_L >= 1
  *                                (P % a_L == 0), columns past Cin read as zero.  Lanes walk positions,
@@ -477,6 +480,16 @@ typedef struct s4g_gemm_desc {
   float *out2;
   int32_t ldc2, split_n;
   float *out_amax2;
+  /* ABI >= 14, optional, S4G_GEMM_LOAD_GATHER_ADD only (S4G_EINVAL with any other loader): a bias PER CENTROID,
+   * (nscenes * M, Cin) fp32 channels-last, 16-byte aligned.  When non-NULL the row of centroid (b, m) uses
+   * cbias[(b*M + m)*Cin + k] in place of mlp1_w[k].w (mlp1_w[k].xyz as before):
+   *   A row p = relu(F[b*N + gidx[p]] + W_xyz . (xyz - ctr) + cbias[b*M + m])
+   * -- the edge levels of MODEL.TYPE "EDGEPN2D", whose first layer W . [rel | f_j | f_j - f_c] + b splits into
+   * W_xyz . rel (this loader), (W_a + W_b) . f_j per point (F) and b - W_b . f_c(m) per centroid (cbias).
+   * F16X2: the three terms are ADDED, so a_amax bounds |F|, a_amax2 |cbias| (the out_amax of the launch that
+   * wrote it) and a_amax_floor the xyz term alone.  NULL: everything as without the member.  The ctypes mirror's
+   * last member is pinned to a_L, so this one sits in front of it. */
+  const float *cbias;
   /* ABI >= 14: S4G_GEMM_LOAD_CHANNEL_FIRST: positions per scene of the (B, Cin, a_L) input (N of a (B, C, N)
    * tensor, M*K of a (B, C, M, K) one).  rows_per_scene = a_L gives per-scene scales. */
   int32_t a_L;

@@ -8,7 +8,9 @@ STRUCTURE, so the reference's own instances qualify too:
   * SharedMLP-shaped: an `nn.ModuleList` of blocks, each with a `.conv` (1x1 `Conv1d` / `Conv2d`, groups 1), a `.bn`
     (BatchNorm1d / 2d with running statistics, or None) and a `.relu` (`nn.ReLU` or None);
   * SA-module-shaped: `num_centroids`, `sampler`, `grouper`, `use_xyz` and a SharedMLP-shaped `mlp` whose last block has
-    a ReLU (`PointNetSAAvgModule` / `EdgeSAModule` share those attributes but not the forward: left alone).
+    a ReLU (`PointNetSAAvgModule` shares those attributes but not the forward: left alone).  An `EdgeSAModule` -- a
+    grouper whose forward takes the centroids' features -- qualifies: it groups through its own grouper (the
+    (B, 2C+3, M, K) tensor [xyz | f_j | f_j - f_c] exists on this path; `FusedPointNet2` never forms it).
 
 A converted module's class becomes a generated subclass of its own class, so identity, hooks, parent references,
 `isinstance` and the `state_dict` stay exactly as they were.  Its forward runs the fast path only in eval mode, on a
@@ -22,10 +24,11 @@ or buffer changes -- `load_state_dict`, in-place edits):
   * SA: `modules.sample_and_group`, then the same chain on the grouped (B, C, M, K) tensor with the max over the K
     neighbours inside the last launch's epilogue (the (B, Cout, M, K) tensor and `torch.max` are gone).
 With "f16x2" every launch needs a per-scene bound of |A|: the first one takes it from the source features (one small
-reduction, `s4g_amax_per_scene_f32`) plus the ball radius for the centred xyz columns, the next ones from the previous
-launch's `out_amax`.  No host synchronisation.  The logit `Conv1d`s and the sigmoid stay torch.
+reduction, `s4g_amax_per_scene_f32`; twice that for an edge module, whose columns f_j - f_c reach 2 max|f|) plus the
+ball radius for the centred xyz columns, the next ones from the previous launch's `out_amax`.  No host synchronisation.  The logit `Conv1d`s and the sigmoid stay torch.
 """
 import ctypes
+import inspect
 
 import torch
 from torch import nn
@@ -33,7 +36,7 @@ from torch import nn
 from . import _cabi
 from . import functions as _F
 from .fused import _Layer, _pad_k, fold_conv_bn
-from .modules import sample_and_group
+from .modules import edge_sample_and_group, sample_and_group
 
 PRECISIONS = {"f16x2": 3, "fp32": 0}
 LOAD_PLAIN, LOAD_CHANNEL_FIRST = 0, 6
@@ -67,7 +70,7 @@ def _is_sa(m):
     if not all(hasattr(m, a) for a in ("num_centroids", "sampler", "grouper", "use_xyz", "mlp")):
         return False
     name = getattr(type(m), "_s4g_base", type(m)).__name__
-    if "Avg" in name or "Edge" in name:
+    if "Avg" in name:
         return False
     return (_is_shared_mlp(m.mlp) and isinstance(m.mlp[0].conv, nn.Conv2d) and m.mlp[-1].relu is not None and
             (m.num_centroids == 0 or hasattr(m.grouper, "radius")))
@@ -195,12 +198,19 @@ def _mlp_forward(self, x):
     return _chain(self, st, x)
 
 
+def _is_edge(sa):
+    """An edge SA module by structure: its grouper's forward takes the centroids' features (reference modules.py:70)."""
+    g = getattr(sa, "grouper", None)
+    return g is not None and "centroid_feature" in inspect.signature(type(g).forward).parameters
+
+
 def _sa_forward(self, xyz, feature=None):
     base = type(self)._s4g_base
     st = self.__dict__.get("_s4g")
     if st is None or not _fast(self, xyz, feature):
         return base.forward(self, xyz, feature)
-    new_xyz, group = sample_and_group(self, xyz, feature)
+    edge = _is_edge(self) and feature is not None and self.num_centroids != 0
+    new_xyz, group = (edge_sample_and_group if _is_edge(self) else sample_and_group)(self, xyz, feature)
     if group.shape[1] != self.mlp[0].conv.in_channels:
         return base.forward(self, xyz, feature)
     B, _, M, K = group.shape
@@ -209,6 +219,10 @@ def _sa_forward(self, xyz, feature=None):
         # |A| per scene: the source features, and for the xyz columns the ball radius (centred coordinates) or,
         # grouping all points, the coordinates themselves -- the grouped tensor is not reduced a second time
         a = _amax(feature.contiguous(), B) if feature is not None else None
+        if edge:
+            # |f_j| <= a and |f_j - f_c| <= 2 a: this loader JOINS its bounds by the maximum, so the feature columns'
+            # bound is 2 a (an exact doubling of the slots on the device)
+            a = a.view(torch.float32) * 2.0
         a2, floor = None, 0.0
         if self.use_xyz:
             if self.num_centroids == 0:

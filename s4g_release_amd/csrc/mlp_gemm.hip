@@ -68,7 +68,14 @@ enum { LOAD_PLAIN = 0, LOAD_GATHER = 1, LOAD_INTERP = 2, LOAD_GATHER_MLP1 = 3, L
        // the 3 -> C first layer runs on the matrix cores too (mlp_chain_kernel, "phase 0")
        LOAD_REL_MLP1 = 64,
        // internal: GATHER_ADD in the f16x2 chain kernel with the xyz term on the matrix cores and the gather a plain copy
-       LOAD_ADD_MFMA0 = 65 };
+       LOAD_ADD_MFMA0 = 65,
+       // internal: GATHER_ADD / ADD_MFMA0 with the loader's bias a row of `cbias` chosen by the row's centroid (the edge
+       // levels of EDGEPN2D: b - W_b . f_c(m)) instead of mlp1[k].w.  Forms of their own, dispatched on d->cbias, so
+       // the instantiations without it keep their code
+       LOAD_GATHER_ADD_CB = 66,
+       LOAD_ADD_MFMA0_CB = 67 };
+constexpr bool is_gather_add(int l) { return l == LOAD_GATHER_ADD || l == LOAD_GATHER_ADD_CB; }
+constexpr bool is_add_mfma0(int l) { return l == LOAD_ADD_MFMA0 || l == LOAD_ADD_MFMA0_CB; }
 enum { EPI_STORE = 0, EPI_MAX = 1, EPI_CHANNEL_FIRST = 2, EPI_MAX_CF = 3 };
 
 struct GemmParams {
@@ -134,7 +141,10 @@ struct GemmParams {
   uint32_t* out_amax;          // 64 slots or NULL
   int rps;                     // loader rows per scene: slot row s of a_amax / out_amax belongs to scene s (0: one row)
   const uint16_t* Wfrag;       // f16x2 planes in MFMA-fragment order (mlp_chain_kernel) or NULL
-  const float* lbias;          // INTERP_ADD loader: bias of the layer whose output the loader forms
+  // INTERP_ADD loader: bias of the layer whose output the loader forms.  GATHER_ADD_CB / ADD_MFMA0_CB (the two loaders
+  // never meet): the (nscenes * M, Cin) per-centroid bias rows read in place of mlp1[k].w -- in this slot so that the
+  // struct, and with it every kernel that existed before those forms, stays as it was
+  const float* lbias;
   // fused second layer (mlp_chain_kernel): out = max_K relu(bn(W2 relu(bn(W A))))
   const uint16_t* Wfrag2;
   const float* w_inv_scale2;
@@ -164,8 +174,17 @@ __device__ __forceinline__ void gather_row_bm(int M, int K, int p0, int r, int& 
   m = (K & (K - 1)) == 0 ? rem >> (31 - __clz(K)) : rem / K;
 }
 
+// GATHER_ADD_CB's per-row state: the row's centroid's bias row.  An empty base everywhere else, so that the other
+// loaders' state -- and the code of the kernels that hold it -- is what it was before this form existed
+template <bool ON, int RPT>
+struct ALoaderCb {
+  const float* cb0[RPT];
+};
+template <int RPT>
+struct ALoaderCb<false, RPT> {};
+
 template <int LOADER, int RPT = 4, int RS = 32>
-struct ALoader {
+struct ALoader : ALoaderCb<LOADER == LOAD_GATHER_ADD_CB, RPT> {
   // per-thread: RPT rows srow(t)+RS*s, one 4-float chunk chunk(t).  Row-major sources: row t>>3, chunk t&7 --
   // eight lanes read one row's 128 bytes.  CHANNEL_FIRST (A[b][k][l]): a wave's lanes walk 32 consecutive
   // positions of one chunk, so each of its four channel loads is a contiguous 128-byte run; the thread's
@@ -182,7 +201,7 @@ struct ALoader {
   size_t drow[RPT];
 
   __device__ __forceinline__ void init(const GemmParams& p, int p0, int g, int t) {
-    constexpr bool GATHERS = LOADER == LOAD_GATHER_MLP1 || LOADER == LOAD_GATHER_ADD || LOADER == LOAD_GATHER;
+    constexpr bool GATHERS = LOADER == LOAD_GATHER_MLP1 || is_gather_add(LOADER) || LOADER == LOAD_GATHER;
     // Pass 1: every row's position and -- for the gathering loaders -- its neighbour index.  The
     // index loads are unconditional (a row past the end reads row 0's) and all issued before the
     // first dependent gather: one round trip for the thread's rows instead of one per row (a
@@ -223,10 +242,12 @@ struct ALoader {
         rel[s][0] = __fsub_rn(x[j], c[m]);
         rel[s][1] = __fsub_rn(x[p.N + j], c[p.M + m]);
         rel[s][2] = __fsub_rn(x[2 * p.N + j], c[2 * p.M + m]);
-      } else if constexpr (LOADER == LOAD_GATHER_ADD) {
+      } else if constexpr (is_gather_add(LOADER)) {
         // first SA layer applied to the level's features BEFORE the grouping (it is linear):
         // A[p][k] = relu(F[b*N + j][k] + w1[k] . (xyz_j - ctr_m, 1))
         src0[s] = p.feat + ((size_t)b * p.N + j) * p.Cf;
+        // (_CB: the 1's coefficient is cbias[b*M + m][k]; a row past the end has the tile's first row's centroid)
+        if constexpr (LOADER == LOAD_GATHER_ADD_CB) this->cb0[s] = p.lbias + ((size_t)b * p.M + m) * p.Cin;
         const float* x = p.xyz + (size_t)b * 3 * p.N;
         const float* c = p.ctr + (size_t)b * 3 * p.M;
         rel[s][0] = __fsub_rn(x[j], c[m]);
@@ -271,18 +292,22 @@ struct ALoader {
       }
       return r;
     }
-    if constexpr (LOADER == LOAD_GATHER_ADD) {
-      // (unconditional loads as above; a row past the end reads row 0's feature row)
+    if constexpr (is_gather_add(LOADER)) {
+      // (unconditional loads as above; a row past the end reads row 0's feature row -- and, _CB, a live bias row)
       const bool live = ok[s] && k0 < p.Cin;
       const int kk = k0 < p.Cin ? k0 : 0;
       const float4 f = *reinterpret_cast<const float4*>(src0[s] + kk);
       const float fv[4] = {f.x, f.y, f.z, f.w};
+      float4 cb = f4zero();
+      if constexpr (LOADER == LOAD_GATHER_ADD_CB) cb = *reinterpret_cast<const float4*>(this->cb0[s] + kk);
+      const float cbv[4] = {cb.x, cb.y, cb.z, cb.w};
       float4 r;
       float* rp = reinterpret_cast<float*>(&r);
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
         const float4 w = p.mlp1[kk + e];
-        const float v = __fmaf_rn(w.z, rel[s][2], __fmaf_rn(w.y, rel[s][1], __fmaf_rn(w.x, rel[s][0], w.w)));
+        const float b1 = LOADER == LOAD_GATHER_ADD_CB ? cbv[e] : w.w;
+        const float v = __fmaf_rn(w.z, rel[s][2], __fmaf_rn(w.y, rel[s][1], __fmaf_rn(w.x, rel[s][0], b1)));
         rp[e] = live ? fmaxf(__fadd_rn(fv[e], v), 0.f) : 0.f;
       }
       return r;
@@ -921,7 +946,7 @@ __global__ __launch_bounds__(256, (NCB == 4 || LOADER == LOAD_INTERP || LOADER =
 
   // activation scale: the power of two that puts the tensor maximum in [2^14, 2^15)
   float amax = PL == 2 ? p.a_amax_floor : 1.f;
-  constexpr bool ADD_BOUNDS = LOADER == LOAD_GATHER_ADD || LOADER == LOAD_INTERP_ADD;   // the loader SUMS its inputs
+  constexpr bool ADD_BOUNDS = is_gather_add(LOADER) || LOADER == LOAD_INTERP_ADD;   // the loader SUMS its inputs
   const int p_hi = min(p0 + GM_BM, p.P) - 1;   // rows of this tile: [p0, p_hi]
   if (PL == 2 && p.a_amax) {
     const float m = amax_rows(p.a_amax, lane, p0, p_hi, p.rps);
@@ -1169,8 +1194,9 @@ __global__ __launch_bounds__(RW == 8 ? 512 : 256, (PL == 1 && RW != 8 && S4G_CHA
   const int wave = t >> 6;
 
   // GATHER_ADD with its vector work on the matrix cores: the gather is a copy into LDS, the xyz term one MFMA step
-  constexpr bool ADD0 = LOADER == LOAD_ADD_MFMA0;
-  constexpr bool ADD_BOUNDS = LOADER == LOAD_GATHER_ADD || LOADER == LOAD_INTERP_ADD || ADD0;   // the loader SUMS its inputs
+  constexpr bool ADD0 = is_add_mfma0(LOADER);
+  constexpr bool CB0 = LOADER == LOAD_ADD_MFMA0_CB;   // ... with the bias slot of the channel operand a per-centroid row
+  constexpr bool ADD_BOUNDS = is_gather_add(LOADER) || LOADER == LOAD_INTERP_ADD || ADD0;   // the loader SUMS its inputs
   constexpr bool MFMA0 = LOADER == LOAD_REL_MLP1;   // the xyz-only first layer as one 16-deep MFMA step (f16x2 form only)
   static_assert(!(MFMA0 || ADD0) || (PL == 2 && KC == 1), "phase 0 on the matrix cores: f16x2, one panel");
   static_assert(!ADD0 || EPI2 == EPI_MAX, "a wave's 64 rows are one centroid's neighbours");
@@ -1264,12 +1290,23 @@ __global__ __launch_bounds__(RW == 8 ? 512 : 256, (PL == 1 && RW != 8 && S4G_CHA
 #pragma unroll
     for (int s = 0; s < RPT; ++s) jg[s] = __builtin_amdgcn_raw_buffer_load_b32(ridx, ((t >> 3) + RS * s) * 4, 0, 0);
     // the wave's centroid and its (rel, 0) records: the same single rounded subtraction as the vector-ALU loader
+    float cb_w = 0.f;   // CB0: this lane's channel of the wave's centroid's bias row
     {
       int bw, mw;
       gather_row_bm(p.M, p.K, p0, __builtin_amdgcn_readfirstlane(wr * WROWS), bw, mw);
       bw = __builtin_amdgcn_readfirstlane(bw);
       mw = __builtin_amdgcn_readfirstlane(mw);
       const bool okw = p0 + wr * WROWS < p.P;
+      if constexpr (CB0) {
+        // the wave's 64 rows are ONE centroid (bw, mw): its bias row rides in the channel operand's fourth slot, so the
+        // R = 2 form's two row-waves carry different channel operands (wv0, s_w and epi_s are per wave already).
+        // A wave past P and a channel past Cin read zeros (the dispatch checks the tensor fits 32-bit offsets)
+        const __amdgpu_buffer_rsrc_t rcb = __builtin_amdgcn_make_buffer_rsrc(
+            const_cast<float*>(p.lbias), 0, p.nscenes * p.M * p.Cin * 4, 0x00020000);
+        const int chb = wc * 64 + lane;
+        cb_w = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(
+                                             rcb, okw && chb < p.Cin ? (uint32_t)((bw * p.M + mw) * p.Cin + chb) * 4u : OOB, 0, 0));
+      }
       float cx = 0.f, cy = 0.f, cz = 0.f;
       if (okw) {
         const float* c = p.ctr + (size_t)bw * 3 * p.M + mw;
@@ -1313,6 +1350,7 @@ __global__ __launch_bounds__(RW == 8 ? 512 : 256, (PL == 1 && RW != 8 && S4G_CHA
     }
     const int ch = wc * 64 + lane;
     if (ch < p.Cin) wv0 = p.mlp1[ch];
+    if constexpr (CB0) wv0.w = cb_w;
   } else if constexpr (MFMA0) {
     const int rows_left = p.P - p0;
     const __amdgpu_buffer_rsrc_t rrel = __builtin_amdgcn_make_buffer_rsrc(
@@ -1941,7 +1979,11 @@ static int launch_gemm_f16x2(const GemmParams& p, int groups, hipStream_t st) {
   const bool wide = force ? force == 4
                           : p.Cout > 256 && wide_wgs >= 512 &&
                                 (LOADER == LOAD_PLAIN || LOADER == LOAD_GATHER_MLP1 || LOADER == LOAD_GATHER_ADD);
-  if (wide) return launch_gemm_f16x2_cfg<LOADER, EPI, 4, PL>(p, groups, st);
+  // (GATHER_ADD_CB holds a bias pointer per row on top of GATHER_ADD's state: it would spill in the wide tile, which is
+  // not even instantiated for it)
+  if constexpr (LOADER != LOAD_GATHER_ADD_CB) {
+    if (wide) return launch_gemm_f16x2_cfg<LOADER, EPI, 4, PL>(p, groups, st);
+  }
   return launch_gemm_f16x2_cfg<LOADER, EPI, 2, PL>(p, groups, st);
 }
 
@@ -2070,7 +2112,7 @@ extern "C" int s4g_mlp_gemm_f32(const s4g_gemm_desc_t* d, s4g_stream_t stream) {
   p.out_amax = (uint32_t*)d->out_amax;
   p.rps = d->rows_per_scene > 0 ? d->rows_per_scene : 0;
   p.Wfrag = (const uint16_t*)d->W_f16x2_frag;
-  p.lbias = d->loader_bias;
+  p.lbias = d->cbias ? d->cbias : d->loader_bias;   // (cbias: GATHER_ADD only, checked below; see GemmParams)
   p.Wfrag2 = (const uint16_t*)d->W2_f16x2_frag;
   p.w_inv_scale2 = d->w2_inv_scale;
   p.bias2 = d->bias2;
@@ -2106,7 +2148,7 @@ extern "C" int s4g_mlp_gemm_f32(const s4g_gemm_desc_t* d, s4g_stream_t stream) {
   } else if (d->loader == S4G_GEMM_LOAD_GATHER_ADD) {
     if (!d->gidx || !d->xyz || !d->ctr || !d->mlp1_w || !d->feat || (d->Cin & 3) || d->Cf != d->Cin ||
         d->K <= 0 || d->M <= 0 || d->N <= 0 || d->groups != 1 || ((uintptr_t)d->mlp1_w & 15) ||
-        ((uintptr_t)d->feat & 15))
+        ((uintptr_t)d->feat & 15) || ((uintptr_t)d->cbias & 15))
       return S4G_EINVAL;
   } else if (d->loader == S4G_GEMM_LOAD_INTERP_ADD) {
     if (!d->nidx || !d->nw || !d->sparse || !d->loader_bias || (d->Cin & 3) || d->C2 != d->Cin ||
@@ -2125,6 +2167,7 @@ extern "C" int s4g_mlp_gemm_f32(const s4g_gemm_desc_t* d, s4g_stream_t stream) {
     return S4G_EINVAL;
   }
   if (d->loader != S4G_GEMM_LOAD_GATHER_MLP1 && (d->seg4 || d->seg_rows)) return S4G_EINVAL;
+  if (d->loader != S4G_GEMM_LOAD_GATHER_ADD && d->cbias) return S4G_EINVAL;   // only the add-loader has a bias to replace
   if (d->out2) {   // second output tensor: plain single layers of the f16x2 / bf16 kernels only
     const bool bf1_ = d->precision == S4G_GEMM_BF16;
     if (!(h2 || bf1_) || d->loader != S4G_GEMM_LOAD_PLAIN || d->epilogue != S4G_GEMM_EPI_STORE || d->W2_f16x2_frag ||
@@ -2178,10 +2221,28 @@ extern "C" int s4g_mlp_gemm_f32(const s4g_gemm_desc_t* d, s4g_stream_t stream) {
     // GATHER_ADD pairs of the f16x2 form: the gather as a copy, the xyz term as one MFMA step (mlp_chain_kernel, ADD0).
     // Its buffer resources take 32-bit byte offsets; a tensor past 2 GiB keeps the vector-ALU loader below.
     if (h2 && d->loader == S4G_GEMM_LOAD_GATHER_ADD && d->epilogue == S4G_GEMM_EPI_MAX && d->Kpad16 == d->Cout &&
-        (int64_t)p.nscenes * d->N * d->Cf * 4 < (1ll << 31) && (int64_t)p.nscenes * d->N * 12 < (1ll << 31))
+        (int64_t)p.nscenes * d->N * d->Cf * 4 < (1ll << 31) && (int64_t)p.nscenes * d->N * 12 < (1ll << 31) &&
+        (int64_t)p.nscenes * d->M * d->Cin * 4 < (1ll << 31)) {
+      if (d->cbias)
+        return c128   ? launch_mlp_chain<LOAD_ADD_MFMA0_CB, EPI_MAX, 2, 1, 2>(p, d->groups, st)
+               : c256 ? launch_mlp_chain<LOAD_ADD_MFMA0_CB, EPI_MAX, 1, 1, 2>(p, d->groups, st)
+                      : launch_mlp_chain<LOAD_ADD_MFMA0_CB, EPI_MAX, 8, 1, 2>(p, d->groups, st);
       return c128   ? launch_mlp_chain<LOAD_ADD_MFMA0, EPI_MAX, 2, 1, 2>(p, d->groups, st)
              : c256 ? launch_mlp_chain<LOAD_ADD_MFMA0, EPI_MAX, 1, 1, 2>(p, d->groups, st)
                     : launch_mlp_chain<LOAD_ADD_MFMA0, EPI_MAX, 8, 1, 2>(p, d->groups, st);
+    }
+    // ... and with a per-centroid bias on the vector-ALU loader (the single-plane form, tensors past 2 GiB): the forms
+    // s4g_gemm_chain_supported lists for GATHER_ADD, with the bias row read beside the F chunk
+    if (d->cbias) {
+      if (d->epilogue != S4G_GEMM_EPI_MAX || d->Kpad16 != d->Cout) return S4G_EUNSUPPORTED;
+#define S4G_FUSED2_CB(R)                                                                        \
+  return bf1 ? launch_mlp_chain<LOAD_GATHER_ADD_CB, EPI_MAX, R, 1, 1>(p, d->groups, st)         \
+             : launch_mlp_chain<LOAD_GATHER_ADD_CB, EPI_MAX, R, 1, 2>(p, d->groups, st);
+      if (c128) { S4G_FUSED2_CB(2) }
+      if (c256) { S4G_FUSED2_CB(1) }
+      S4G_FUSED2_CB(8)
+#undef S4G_FUSED2_CB
+    }
 #define S4G_FUSED2_CASE(L, E, R, KCH)                                                        \
   if (d->loader == L && (int)d->epilogue == (int)E && (c128 ? 2 : (c256 ? 1 : 8)) == R &&     \
       d->Kpad16 / d->Cout == KCH)                                                             \
@@ -2229,6 +2290,19 @@ extern "C" int s4g_mlp_gemm_f32(const s4g_gemm_desc_t* d, s4g_stream_t stream) {
            : (p.bf16_single && bf16_tiled) ? launch_gemm_f16x2<L, E, 1>(p, d->groups, st) \
            : split ? launch_gemm_bf16x3<L, E>(p, d->groups, st)        \
                    : launch_gemm<L, E>(p, d->groups, st);
+  if (d->cbias) {   // (the loader is GATHER_ADD: checked above)
+    if (d->epilogue == EPI_STORE)
+      return h2 ? launch_gemm_f16x2<LOAD_GATHER_ADD_CB, EPI_STORE>(p, d->groups, st)
+             : p.bf16_single ? launch_gemm_f16x2<LOAD_GATHER_ADD_CB, EPI_STORE, 1>(p, d->groups, st)
+             : split ? launch_gemm_bf16x3<LOAD_GATHER_ADD_CB, EPI_STORE>(p, d->groups, st)
+                     : launch_gemm<LOAD_GATHER_ADD_CB, EPI_STORE>(p, d->groups, st);
+    if (d->epilogue == EPI_MAX)
+      return h2 ? launch_gemm_f16x2<LOAD_GATHER_ADD_CB, EPI_MAX>(p, d->groups, st)
+             : p.bf16_single ? launch_gemm_f16x2<LOAD_GATHER_ADD_CB, EPI_MAX, 1>(p, d->groups, st)
+             : split ? launch_gemm_bf16x3<LOAD_GATHER_ADD_CB, EPI_MAX>(p, d->groups, st)
+                     : launch_gemm<LOAD_GATHER_ADD_CB, EPI_MAX>(p, d->groups, st);
+    return S4G_EUNSUPPORTED;
+  }
   S4G_GEMM_CASE(LOAD_PLAIN, EPI_STORE)
   S4G_GEMM_CASE(LOAD_PLAIN, EPI_MAX)
   S4G_GEMM_CASE(LOAD_PLAIN, EPI_CHANNEL_FIRST)

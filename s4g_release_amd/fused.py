@@ -29,6 +29,10 @@ torch's operator set.  What a forward pass launches (round 3, default f16x2 arit
   * the contact network (`MODEL.TYPE: "PN2"`, `model.ContactPointNet2`): the heads write the raw 17 logit channels,
     then ONE elementwise launch (`s4g_contact_heads_f32`) forms the rotation matrices from the 6-D logits and adds
     the points to the offsets;
+  * the edge network (`MODEL.TYPE: "EDGEPN2D"`, `model.EdgePointNet2Down`): from level 1 on a neighbour's row is
+    [xyz_j - c_m | f_j | f_j - f_c(m)]; the linear first layer splits into W_x . rel (the loader), (W_a + W_b) . f_j once
+    per point (`sa{l}.0f`) and b - W_b . f_c(m) once per centroid (`sa{l}.0c`, one short launch more per edge level),
+    which the chain launch's loader reads as a per-centroid bias (`s4g_gemm_desc_t.cbias`) -- `_fold_edge_level`;
 Twelve contraction launches per forward pass.  `submit()` runs the coordinate-only work (FPS
 pyramid, ball queries, 3-NN) on high-priority geometry streams underneath the previous batch's
 contractions.
@@ -61,20 +65,21 @@ CONTACT_RAW_CHANNELS = (3, 6, 3, 5)      # what s4g_contact_heads_f32 reads ...
 CONTACT_OUT_CHANNELS = (3, 9, 3, 5)      # ... and writes
 
 
-def fold_conv_bn(block):
-    """(W', b') of one conv->bn(->relu) block, fp64 folding rounded once to fp32."""
+def fold_conv_bn(block, dtype=torch.float32):
+    """(W', b') of one conv->bn(->relu) block, fp64 folding rounded once to fp32 (dtype=torch.float64: not rounded,
+    for a caller that folds further before the one rounding)."""
     w = block.conv.weight.detach().double().flatten(1)      # (Cout, Cin)
     if block.bn is None:
         b = block.conv.bias.detach().double() if block.conv.bias is not None else \
             torch.zeros(w.shape[0], dtype=torch.float64, device=w.device)
-        return w.float(), b.float()
+        return w.to(dtype), b.to(dtype)
     bn = block.bn
     scale = bn.weight.detach().double() / torch.sqrt(bn.running_var.detach().double() + bn.eps)
     wf = w * scale[:, None]
     bf = bn.bias.detach().double() - bn.running_mean.detach().double() * scale
     if block.conv.bias is not None:
         bf = bf + block.conv.bias.detach().double() * scale
-    return wf.float(), bf.float()
+    return wf.to(dtype), bf.to(dtype)
 
 
 def _pad_k(w, mult=8):
@@ -169,8 +174,9 @@ class FusedPointNet2:
     """Callable with the reference forward's signature: {"scene_points": (B,3,N)} -> dict."""
 
     def __init__(self, net, precision=None, fold_only=False, check_finite=False):
-        """net: `model.PointNet2` / `model.ContactPointNet2`, or the reference's own `PointNet2_tcls.PointNet2` /
-        `PointNet2.PointNet2` instance.  The kind is read from the logit widths: R_logit / t_logit 9 / 4 = the
+        """net: `model.PointNet2` / `model.ContactPointNet2` / `model.EdgePointNet2Down`, or the reference's own
+        `PointNet2_tcls.PointNet2` / `PointNet2.PointNet2` / `EdgePointNet2Down.EdgePointNet2Down` instance (an edge
+        level is read from the structure: a first conv of 2 C + 3 inputs, C the previous level's output width).  The kind is read from the logit widths: R_logit / t_logit 9 / 4 = the
         curvature model (PN2_CLS, outputs score / frame_R / frame_t / movable_logits as its forward), 6 / 3 = the
         contact model (PN2: scene_score_logits / frame_R (rotation matrices) / frame_t (points + offsets) /
         movable_logits, as `PointNet2.py:142-147`); any other pair raises ValueError.  (The attributes read
@@ -231,16 +237,25 @@ class FusedPointNet2:
         if not fold_only:
             _cabi.lib()
         self.sa = []
+        c_prev = 0
         for sa in net.sa_modules:
             if sa.sampler is None or sa.grouper is None:
                 raise NotImplementedError("fast path covers sampled + grouped SA modules only")
             if sa.grouper.num_neighbours not in (16, 32, 64):
                 raise NotImplementedError("fast path needs num_neighbours in {16, 32, 64}")
+            # (the reference's EdgeSAModule keeps no `in_channels`: the level's input width is the previous level's output)
+            sa_in = int(getattr(sa, "in_channels", c_prev))
+            c_prev = sa.mlp[-1].conv.out_channels
+            # an EDGE level by structure: the first conv takes [xyz | f_j | f_j - f_c] = 2 C + 3 inputs (modules.py:84)
+            edge = sa_in > 0 and sa.mlp[0].conv.in_channels == 2 * sa_in + 3
+            if edge:
+                self.sa.append(self._fold_edge_level(sa, sa_in))
+                continue
             layers = []
             mlp1 = None
             for li, blk in enumerate(sa.mlp):
                 w, b = fold_conv_bn(blk)
-                if li == 0 and sa.in_channels == 0 and len(sa.mlp) > 1 and w.shape[0] % 4 == 0:
+                if li == 0 and sa_in == 0 and len(sa.mlp) > 1 and w.shape[0] % 4 == 0:
                     # xyz-only first layer (3 -> C1): evaluated inside the next layer's
                     # loader (3 fmas per channel) instead of a launch that writes
                     # (B*M*K, C1) to HBM and reads it back
@@ -254,14 +269,14 @@ class FusedPointNet2:
                 layers.append(_Layer(_pad_k(w), b, cin))
             radius = float(sa.grouper.radius)
             pre = None
-            if (sa.in_channels > 0 and sa.in_channels % 4 == 0 and len(sa.mlp) > 1 and
+            if (sa_in > 0 and sa_in % 4 == 0 and len(sa.mlp) > 1 and
                     layers[0].cout % 4 == 0 and _cabi.knob("S4G_SA_LINEAR_FIRST", "1") != "0"):
                 # a level WITH input features: its first layer is linear, so the feature part is
                 # applied once per POINT (N rows) instead of once per (centroid, neighbour) pair
                 # (M*K rows, every point ~K*M/N times); the xyz part + bias + ReLU move into the
                 # next layer's loader
                 w0 = layers[0].W[:, :layers[0].cin]                 # K order [feat, xyz]
-                cf = sa.in_channels
+                cf = sa_in
                 la = _Layer(_pad_k(w0[:, :cf].contiguous()), torch.zeros_like(layers[0].bias), cf)
                 w1 = torch.cat([w0[:, cf:cf + 3], layers[0].bias[:, None]], dim=1).contiguous()
                 bound = float((w1[:, :3].abs().sum(dim=1) * radius + w1[:, 3].abs()).max())
@@ -271,7 +286,7 @@ class FusedPointNet2:
                 (mlp1[:, :3].abs().sum(dim=1) * radius + mlp1[:, 3].abs()).max())
             self.sa.append(dict(M=sa.num_centroids, radius=radius,
                                 K=int(sa.grouper.num_neighbours), layers=layers,
-                                cf=sa.in_channels, mlp1=mlp1, mlp1_bound=mlp1_bound, pre=pre))
+                                cf=sa_in, mlp1=mlp1, mlp1_bound=mlp1_bound, pre=pre, edge=False))
         self.fp = []
         for fp in net.fp_modules:
             if fp.interpolator is None:
@@ -335,6 +350,42 @@ class FusedPointNet2:
                 bpad[h, :c] = lg.bias.detach()
             self.heads_fused = list(hl) + [_Layer(wpad, bpad, cl, groups=4)]
 
+    @staticmethod
+    def _fold_edge_level(sa, cf):
+        """An edge level (`EdgeSAModule`, reference modules.py:407-475): the grouped row of neighbour j of centroid m
+        is [rel | f_j | f_j - f_c(m)] and the first layer is linear, so
+
+          W . [rel | f_j | f_j - f_c] + b  =  W_x . rel  +  (W_a + W_b) . f_j  +  (b - W_b . f_c(m))
+
+        `la` = W_a + W_b (summed in float64, rounded once) runs once per POINT (`sa{l}.0f`), `lc` = -W_b with bias b
+        once per CENTROID (`sa{l}.0c`, its output the loader's `cbias`), and `w1` = [W_x | b] goes to the loader as
+        for a plain level (its bias column is not read when `cbias` is given).  The (B, 2C+3, M, K) tensor is never
+        formed and f_j - f_c is never rounded.  The only form of an edge level on this path."""
+        if len(sa.mlp) < 2 or cf % 4 or sa.mlp[0].conv.out_channels % 4:
+            raise NotImplementedError("fast path: an edge SA level needs >= 2 layers and input / first-layer widths "
+                                      "that are multiples of 4")
+        if _cabi.knob("S4G_SA_LINEAR_FIRST", "1") == "0":
+            raise NotImplementedError("fast path: an edge SA level only has the linear-first form "
+                                      "(S4G_SA_LINEAR_FIRST=0 asks for the grouped one)")
+        w64, b64 = fold_conv_bn(sa.mlp[0], torch.float64)            # columns [xyz(3) | W_a(cf) | W_b(cf)]
+        wx, wa, wb = w64[:, :3], w64[:, 3:3 + cf], w64[:, 3 + cf:]
+        b = b64.float()
+        la = _Layer(_pad_k((wa + wb).float().contiguous()), torch.zeros_like(b), cf)
+        lc = _Layer(_pad_k((-wb).float().contiguous()), b, cf)
+        w1 = torch.cat([wx.float(), b[:, None]], dim=1).contiguous()
+        radius = float(sa.grouper.radius)
+        # the loader's own term is the xyz part alone: |w . rel| <= (|wx|+|wy|+|wz|) r inside the ball
+        bound = float((w1[:, :3].abs().sum(dim=1) * radius).max())
+        # layers[0] is never launched (there is no grouped form): it carries the first layer's widths and bias
+        layers = [_Layer(_pad_k(torch.cat([la.W[:, :cf], w1[:, :3]], dim=1)), b, cf + 3)]
+        for blk in list(sa.mlp)[1:]:
+            w, bb = fold_conv_bn(blk)
+            layers.append(_Layer(_pad_k(w), bb, w.shape[1]))
+        # fold64: the same three pieces BEFORE the one rounding (tests check the algebra on them to 1e-12)
+        fold64 = dict(la=wa + wb, lc=-wb, w1=torch.cat([wx, b64[:, None]], dim=1))
+        return dict(M=sa.num_centroids, radius=radius, K=int(sa.grouper.num_neighbours), layers=layers, cf=cf,
+                    mlp1=None, mlp1_bound=0.0, pre=dict(la=la, w1=w1, bound=bound, lc=lc, fold64=fold64), edge=True)
+
     def packed_weights(self):
         """{name: tensor} of every folded / split / fragment-ordered weight tensor the launches read -- what must
         be equal for two networks to run the same forward (tests/test_reference_dropin.py)."""
@@ -353,6 +404,8 @@ class FusedPointNet2:
             if sa["pre"] is not None:
                 put("sa%d.pre" % li, sa["pre"]["la"])
                 out["sa%d.pre.w1" % li] = sa["pre"]["w1"]
+                if sa["edge"]:
+                    put("sa%d.pre.lc" % li, sa["pre"]["lc"])
             out["sa%d.meta" % li] = torch.tensor([sa["M"], sa["K"], sa["cf"], sa["radius"], sa["mlp1_bound"],
                                                   0.0 if sa["pre"] is None else sa["pre"]["bound"]],
                                                  dtype=torch.float64)
@@ -704,7 +757,7 @@ class FusedPointNet2:
         level_xyz, level_n = geo["level_xyz"], geo["level_n"]
         keep = geo.get("feats")                      # return_intermediates: every level feature tensor that exists
         n_launch = sum(len(sa["layers"]) for sa in self.sa) + \
-            sum(len(fp["layers"]) for fp in self.fp) + len(self.head_layers) + 1 + len(self.sa) + 2 * len(self.fp)
+            sum(len(fp["layers"]) for fp in self.fp) + len(self.head_layers) + 1 + 2 * len(self.sa) + 2 * len(self.fp)
         amax = torch.zeros((n_launch, B, 64), dtype=torch.float32, device=dev)
         rows = iter(amax.unbind(0))
         level_feat = [(None, None)]                  # (tensor, amax row)
@@ -720,7 +773,8 @@ class FusedPointNet2:
             x = x_amax = None
             # the last two layers as ONE launch (C -> C -> Cout2 with C = 128 or 256, intermediate
             # in LDS); the first of the pair then reads through the MLP1 or the plain loader
-            pre = sa["pre"] if self.precision in ("f16x2", "bf16") else None
+            # (an edge level has this form only: in every precision)
+            pre = sa["pre"] if (self.precision in ("f16x2", "bf16") or sa["edge"]) else None
             lp = len(layers) - 2                  # first layer of the candidate pair
             first_loader = (LOAD_GATHER_MLP1 if (lp == 1 and sa["mlp1"] is not None) else
                             LOAD_GATHER_ADD if (lp == 1 and pre is not None) else LOAD_PLAIN)
@@ -744,6 +798,18 @@ class FusedPointNet2:
                     self._gemm("sa%d.0f" % li, pre["la"], B * level_n[li], LOAD_PLAIN, EPI_STORE, relu=False,
                                out=fpre, ldc=layers[0].cout, A=feat, lda=feat.shape[1], a_amax=feat_amax,
                                out_amax=fpre_amax)
+                cbias = cbias_amax = None
+                if sa["edge"]:
+                    # cbias = b - W_b . f_c(m), one row per centroid: the rows FPS picked, through a plain launch
+                    # that publishes max |cbias| per scene for the loader's bound
+                    fidx = geo["sa"][li][0]
+                    flat = (fidx.long() + torch.arange(B, device=dev).view(B, 1) * level_n[li]).reshape(-1)
+                    cfeat = feat.index_select(0, flat)
+                    cbias = torch.empty((B * M, layers[0].cout), dtype=torch.float32, device=dev)
+                    cbias_amax = next(rows)
+                    self._gemm("sa%d.0c" % li, pre["lc"], B * M, LOAD_PLAIN, EPI_STORE, relu=False, out=cbias,
+                               ldc=layers[0].cout, A=cfeat, lda=cfeat.shape[1], a_amax=feat_amax,
+                               out_amax=cbias_amax)
             for l, layer in enumerate(layers):
                 if l == 0 and (sa["mlp1"] is not None or pre is not None):
                     continue                      # folded into layer 1's loader
@@ -771,7 +837,7 @@ class FusedPointNet2:
                 elif l == 1 and pre is not None:
                     kw.update(gidx=gidx, feat=fpre, Cf=layers[0].cout, xyz=level_xyz[li], ctr=ctr,
                               N=level_n[li], M=M, mlp1_w=pre["w1"], a_amax=fpre_amax,
-                              a_amax_floor=pre["bound"])
+                              a_amax_floor=pre["bound"], cbias=cbias, a_amax2=cbias_amax)
                     loader = LOAD_GATHER_ADD
                 elif l == 0:
                     kw.update(gidx=gidx, feat=feat, xyz=level_xyz[li], ctr=ctr, Cf=sa["cf"],

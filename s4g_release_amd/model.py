@@ -1,6 +1,8 @@
-"""The S4G networks: `MODEL.TYPE: "PN2_CLS"` (the curvature model, `PointNet2`) and `MODEL.TYPE: "PN2"` (the
-contact model, `ContactPointNet2`) -- 3 set-abstraction layers, 3 feature-propagation layers and four per-point
-heads; the two differ only after the last logit layer of the rotation and translation heads.
+"""The S4G networks: `MODEL.TYPE: "PN2_CLS"` (the curvature model, `PointNet2`), `MODEL.TYPE: "PN2"` (the
+contact model, `ContactPointNet2`) and `MODEL.TYPE: "EDGEPN2D"` (`EdgePointNet2Down`: the contact model with
+edge-convolution set abstraction, reference `models/EdgePointNet2Down.py`) -- 3 set-abstraction layers, 3
+feature-propagation layers and four per-point heads; the first two differ only after the last logit layer of the
+rotation and translation heads.
 
 Mirror of reference `network_models/models/PointNet2_tcls.py:10-153` (class
 `PointNet2`) with the hyper-parameters of
@@ -21,7 +23,7 @@ from typing import Tuple
 import torch
 from torch import nn
 
-from .modules import PointNetSAModule, PointnetFPModule
+from .modules import EdgeSAModule, PointNetSAModule, PointnetFPModule
 from .nn_utils import SharedMLP
 
 
@@ -159,13 +161,23 @@ class ContactPointNet2(PointNet2):
                 "movable_logits": pred["movable_logits"]}
 
 
-MODEL_TYPES = {"PN2_CLS": PointNet2, "PN2": ContactPointNet2}
+class EdgePointNet2Down(ContactPointNet2):
+    """The edge-convolution network (`MODEL.TYPE: "EDGEPN2D"`, reference network_models/models/EdgePointNet2Down.py):
+    the contact network with `EdgeSAModule` set abstraction -- from level 1 on a neighbour's row is
+    [xyz_j - c_m | f_j | f_j - f_c(m)], so those levels' first conv takes 2 C + 3 inputs.  Same FP modules, heads and
+    outputs as `ContactPointNet2`."""
+    _SA_MODULE = EdgeSAModule
+
+
+MODEL_TYPES = {"PN2_CLS": PointNet2, "PN2": ContactPointNet2, "EDGEPN2D": EdgePointNet2Down}
 
 
 def build_model(model_type, cfg=None):
     """The network of a `MODEL.TYPE` (reference grasp_detector.py:23,36): "PN2_CLS" -> `PointNet2` (curvature
-    model), "PN2" -> `ContactPointNet2` (contact model); `cfg` an `S4GConfig` (default: the shipped values, which
-    both configs share).  Any other type raises ValueError."""
+    model), "PN2" -> `ContactPointNet2` (contact model), "EDGEPN2D" -> `EdgePointNet2Down` (the contact model with
+    edge-convolution set abstraction); `cfg` an `S4GConfig` (default: the shipped values, which the configs share).
+    Any other type raises ValueError -- among them "EDGEPN2DU" (not constructible in the reference either) and
+    "PN2_LOCAL" (needs label-search inputs at inference)."""
     if model_type not in MODEL_TYPES:
         raise ValueError("unsupported MODEL.TYPE %r: expected one of %s" % (model_type, sorted(MODEL_TYPES)))
     cfg = cfg or S4GConfig()

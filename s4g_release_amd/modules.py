@@ -6,9 +6,13 @@ reference's `pointnet2_utils/modules.py`:
   FeatureInterpolator   :96-132    PointNetSAModule   :174-250
   PointnetFPModule      :477-510
 
+and the two `EDGEPN2D` adds to them:
+
+  EdgeQueryGrouper      :63-93     EdgeSAModule       :407-475
+
 Same constructor arguments, forward signatures, return values and (empty)
-parameter sets.  The Avg/MSG/Edge* variants are out of scope (not instantiated
-by either shipped yaml).
+parameter sets.  The Avg/MSG variants and `EdgeFPModule` are out of scope (not
+instantiated by a network whose forward runs).
 """
 import torch
 from torch import nn
@@ -119,6 +123,91 @@ class PointNetSAModule(nn.Module):
 
     def forward(self, xyz, feature=None):
         new_xyz, group_feature = sample_and_group(self, xyz, feature)
+        new_feature = self.mlp(group_feature)
+        new_feature, _ = torch.max(new_feature, 3)
+        return new_xyz, new_feature
+
+    def init_weights(self, init_fn=None):
+        self.mlp.init_weights(init_fn)
+
+    def extra_repr(self):
+        return "num_centroids={:d}, use_xyz={}".format(self.num_centroids, self.use_xyz)
+
+
+class EdgeQueryGrouper(nn.Module):
+    """`QueryGrouper` with the edge term of reference modules.py:63-93: a neighbour's row is
+    [xyz_j - c_m | f_j | f_j - f_c(m)], `centroid_feature` (B, C, M) being the feature of the point FPS picked."""
+
+    def __init__(self, radius, num_neighbours):
+        super().__init__()
+        assert radius > 0.0 and num_neighbours > 0
+        self.radius = radius
+        self.num_neighbours = num_neighbours
+
+    def forward(self, new_xyz, xyz, centroid_feature, feature, use_xyz):
+        with torch.no_grad():
+            index, _ = _F.ball_query(xyz, new_xyz, self.radius, self.num_neighbours)
+        group_xyz = _F.group_points(xyz, index)           # (B, 3, M, K)
+        group_xyz -= new_xyz.unsqueeze(-1)                # centroid-relative (modules.py:77)
+        if feature is None:
+            return group_xyz, group_xyz
+        group_feature = _F.group_points(feature, index)   # (B, C, M, K)
+        group_feature2 = group_feature - centroid_feature.unsqueeze(-1)
+        if use_xyz:
+            group_feature = torch.cat([group_xyz, group_feature, group_feature2], dim=1)   # (:84)
+        else:
+            group_feature = torch.cat([group_feature, group_feature2], dim=1)
+        return group_feature, group_xyz
+
+    def extra_repr(self):
+        return "radius={}, num_neighbours={}".format(self.radius, self.num_neighbours)
+
+
+def edge_sample_and_group(sa, xyz, feature=None):
+    """The sample-and-group half of `EdgeSAModule.forward` (reference modules.py:450-471), on the attributes the
+    reference's own instances have too: (new_xyz (B, 3, M), group_feature (B, 2C + 3, M, K))."""
+    if sa.num_centroids == 0:
+        # one group holding every point, centred at the origin: no centroid feature, no edge term (:450-457)
+        assert sa.grouper is None
+        new_xyz = xyz.new_zeros(xyz.size(0), 3, 1)
+        group_feature = feature.unsqueeze(2)
+        if sa.use_xyz:
+            group_feature = torch.cat([xyz.unsqueeze(2), group_feature], dim=1)
+        return new_xyz, group_feature
+    if sa.num_centroids == -1:
+        new_xyz, centroid_feature = xyz, feature          # every point its own centroid
+    else:
+        index = sa.sampler(xyz)
+        new_xyz = _F.gather_points(xyz, index)
+        centroid_feature = _F.gather_points(feature, index) if feature is not None else None
+    group_feature, _ = sa.grouper(new_xyz, xyz, centroid_feature, feature, use_xyz=sa.use_xyz)
+    return new_xyz, group_feature
+
+
+class EdgeSAModule(nn.Module):
+    """Set abstraction with edge features (reference modules.py:407-475): the first conv of a level with features
+    takes `2 * in_channels + 3` inputs in the order [xyz, f_j, f_j - f_c]; with `num_centroids == 0` (group all)
+    there is no edge term and it takes `in_channels + 3`."""
+
+    def __init__(self, in_channels, mlp_channels, num_centroids, radius, num_neighbours, use_xyz):
+        super().__init__()
+        self.in_channels = in_channels
+        if num_centroids != 0:
+            in_channels *= 2
+        self.out_channels = mlp_channels[-1]
+        self.num_centroids = num_centroids
+        self.use_xyz = use_xyz
+        self.mlp = SharedMLP(in_channels + (3 if use_xyz else 0), mlp_channels, ndim=2, bn=True)
+        self.sampler = FarthestPointSampler(num_centroids) if num_centroids > 0 else None
+        if num_neighbours < 0:
+            assert radius < 0.0
+            self.grouper = None
+        else:
+            assert num_neighbours > 0 and radius > 0.0
+            self.grouper = EdgeQueryGrouper(radius, num_neighbours)
+
+    def forward(self, xyz, feature=None):
+        new_xyz, group_feature = edge_sample_and_group(self, xyz, feature)
         new_feature = self.mlp(group_feature)
         new_feature, _ = torch.max(new_feature, 3)
         return new_xyz, new_feature
