@@ -1524,6 +1524,61 @@ int s4g_process_views_f32(const float *xyz_b3n, const int32_t *count_b /* may be
                           float radius, int32_t nb_points, float *points_out_b3n, int32_t *index_out_bn,
                           int32_t *counts_out_b3, void *ws, size_t ws_bytes, int flags, s4g_stream_t stream);
 
+/* The training objective and metric of the three networks, fused (csrc/loss.hip; added under ABI 14 with no layout
+ * change): PointNet2Loss / PointNet2Metric of the reference's network_models/models/PointNet2_tcls.py:156-267
+ * (variant 0, the curvature model) and PointNet2.py:156-258 (variant 1, the contact and edge models), with
+ * smooth_cross_entropy of nn_utils/functional.py:91-114.  One descriptor drives both entries; every tensor is
+ * contiguous and on the device, predictions and gradients fp32.
+ *   s4g_grasp_loss_f32: losses[4] = cls, R, t, mov, and the UNIT gradient of each loss with respect to its own
+ *   prediction tensor (g_score / g_R / g_t / g_movable, in the tensors' shapes; a NULL pointer skips that store).
+ *     cls, label_smoothing == 0: torch's weighted mean, sum_i w[y_i] nll_i / sum_i w[y_i]; label -100 is in neither sum.
+ *     cls, label_smoothing > 0: s_c = [c == y](1 - ls) + ls / C, per point -sum_c s_c w_c logp_c (the weight by class),
+ *       plain mean over B N.
+ *     mov: mean |p - y| over B D N; gradient sign(p - y) / (B D N), sign(0) = 0.
+ *     R: over the first F points, L1 = mean_9 (p - g)^2, L2 the same with channels 1, 2, 4, 5, 7, 8 of g negated,
+ *       mean_{B F}(min(L1, L2) scene_score) 5; a tie takes L1; the gradient is zero from point F on.
+ *     t: variant 0, cross entropy of frame_t[:, :, :F] against int64 labels (B, F), unweighted, -100 ignored, times 0.2;
+ *       variant 1, mean_{B F}(sum_3 (p - g)^2 scene_score) 20 against fp32 labels (B, 3, F).
+ *   A class label outside its range that is not -100 contributes nothing, gets a zero gradient and sets bit 0 of
+ *   status[0] (bit 1 for best_frame_t); status[0] is written by every call.  F == 0, or every label ignored, gives NaN
+ *   losses and zero gradients, as torch.  Non-finite predictions propagate through their own point only.
+ *   s4g_grasp_metric_f32: cls_acc (B N) and mov_acc (B D N) floats of 0 / 1 (argmax with the lowest index on a tie;
+ *   (p > 0.5) against int(label)), metrics[0] = R_err = mean_{B F}(scene_score min(angle, angle_inv)) with
+ *   angle = acos(clamp((sum_9 g p - 1) / 2, -1, 1)), and t_acc (B F) for variant 0 or metrics[1] = t_err =
+ *   mean sqrt(sum_3 (g - p)^2) for variant 1.
+ * The result is a function of the inputs alone: per-point terms in fp32, one double partial per loss and fixed tile of
+ * 1 024 points, the partials summed in tile order by one workgroup and rounded to fp32 once; no float atomics.
+ * Limits: 1 <= B <= 65 535, N >= 1, B N < 2^31, 0 <= F <= N, 2 <= C <= 8, 1 <= D <= 8, 2 <= Ct <= 8 (variant 0) or
+ * Ct == 3 (variant 1), scene_score_stride >= F, 0 <= label_smoothing < 1 (S4G_EINVAL).  Workspace:
+ * s4g_grasp_loss_workspace_bytes(B, N, F) bytes (0 outside the limits; S4G_EWORKSPACE below that), 256-byte aligned;
+ * contents undefined between calls.  Every refusal happens before the first launch; no host read. */
+typedef struct s4g_loss_desc {
+  int32_t variant;                /* 0 curvature, 1 contact */
+  int32_t B, N, F, C, D, Ct;
+  int32_t scene_score_stride;     /* floats between the rows of scene_score */
+  float label_smoothing;
+  float w[8];                     /* class weights of the score loss, w[0 .. C) */
+  const float *score_logits;      /* (B, C, N) */
+  const float *movable;           /* (B, D, N), after the sigmoid */
+  const float *frame_R;           /* (B, 9, N) */
+  const float *frame_t;           /* (B, Ct, N) */
+  const int64_t *score_labels;    /* (B, N) */
+  const float *movable_labels;    /* (B, D, N) */
+  const float *best_frame_R;      /* (B, 9, F) */
+  const void *best_frame_t;       /* variant 0: int64 (B, F); variant 1: fp32 (B, 3, F) */
+  const float *scene_score;       /* (B, >= F): row b starts at b * scene_score_stride */
+  float *losses;                  /* loss entry: 4 */
+  float *g_score, *g_movable, *g_R, *g_t; /* loss entry: may be NULL */
+  int32_t *status;                /* loss entry: 1 */
+  float *cls_acc, *mov_acc, *t_acc;       /* metric entry: (B N), (B D N), (B F; variant 0) */
+  float *metrics;                 /* metric entry: 2 = R_err, t_err (0 for variant 0) */
+  void *ws;
+  size_t ws_bytes;
+} s4g_loss_desc_t;
+size_t s4g_grasp_loss_workspace_bytes(int64_t B, int64_t N, int64_t F);
+int s4g_grasp_loss_f32(const s4g_loss_desc_t *desc, s4g_stream_t stream);
+int s4g_grasp_metric_f32(const s4g_loss_desc_t *desc, s4g_stream_t stream);
+
 /* ---------------------------------------------------------------------------
  * The operators in DOUBLE (ABI >= 8).  The reference's extension dispatches every kernel over float and
  * double (AT_DISPATCH_FLOATING_TYPES: sampling_kernel.cu:148-167, ball_query_kernel.cu:116-128,

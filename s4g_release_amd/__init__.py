@@ -210,3 +210,34 @@ def FusedPointNetGPD(*args, **kwargs):
     """`baselines.PointNetGPDClassifier` in eval mode on the HIP kernels.  See `baselines.FusedPointNetGPD`."""
     from .baselines import FusedPointNetGPD as _Fused
     return _Fused(*args, **kwargs)
+
+
+def build_loss(*args, **kwargs):
+    """(loss, metric) of a `MODEL.TYPE`: the networks' training objective and metric on one fused HIP call.  See
+    `losses.build_loss`."""
+    from .losses import build_loss as _build
+    return _build(*args, **kwargs)
+
+
+def PointNet2Loss(*args, **kwargs):
+    """The curvature model's objective.  See `losses.PointNet2Loss`."""
+    from .losses import PointNet2Loss as _Loss
+    return _Loss(*args, **kwargs)
+
+
+def PointNet2Metric(*args, **kwargs):
+    """The curvature model's metric.  See `losses.PointNet2Metric`."""
+    from .losses import PointNet2Metric as _Metric
+    return _Metric(*args, **kwargs)
+
+
+def ContactPointNet2Loss(*args, **kwargs):
+    """The contact and edge models' objective.  See `losses.ContactPointNet2Loss`."""
+    from .losses import ContactPointNet2Loss as _Loss
+    return _Loss(*args, **kwargs)
+
+
+def ContactPointNet2Metric(*args, **kwargs):
+    """The contact and edge models' metric.  See `losses.ContactPointNet2Metric`."""
+    from .losses import ContactPointNet2Metric as _Metric
+    return _Metric(*args, **kwargs)

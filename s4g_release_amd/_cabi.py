@@ -68,6 +68,20 @@ class HeadsDesc(ctypes.Structure):
     ]
 
 
+class LossDesc(ctypes.Structure):
+    """ctypes mirror of `s4g_loss_desc_t` (include/s4g_ops.h)."""
+    _fields_ = [
+        ("variant", _i32), ("B", _i32), ("N", _i32), ("F", _i32), ("C", _i32), ("D", _i32), ("Ct", _i32),
+        ("scene_score_stride", _i32), ("label_smoothing", _f32), ("w", _f32 * 8),
+        ("score_logits", _vp), ("movable", _vp), ("frame_R", _vp), ("frame_t", _vp),
+        ("score_labels", _vp), ("movable_labels", _vp), ("best_frame_R", _vp), ("best_frame_t", _vp),
+        ("scene_score", _vp),
+        ("losses", _vp), ("g_score", _vp), ("g_movable", _vp), ("g_R", _vp), ("g_t", _vp), ("status", _vp),
+        ("cls_acc", _vp), ("mov_acc", _vp), ("t_acc", _vp), ("metrics", _vp),
+        ("ws", _vp), ("ws_bytes", _sz),
+    ]
+
+
 # name -> (restype, argtypes); mirrors include/s4g_ops.h one to one.
 SIGNATURES = {
     "s4g_mlp_gemm_f32": (_int, [ctypes.POINTER(GemmDesc), _vp]),
@@ -195,6 +209,9 @@ SIGNATURES = {
     "s4g_process_views_f32": (_int, [_vp, _vp, _i64, _i64, ctypes.POINTER(ctypes.c_float), _f32,
                                      ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_int32), _f32, _i32, _vp,
                                      _vp, _vp, _vp, _sz, _int, _vp]),
+    "s4g_grasp_loss_workspace_bytes": (_sz, [_i64, _i64, _i64]),
+    "s4g_grasp_loss_f32": (_int, [ctypes.POINTER(LossDesc), _vp]),
+    "s4g_grasp_metric_f32": (_int, [ctypes.POINTER(LossDesc), _vp]),
     "s4g_abi_version": (_int, []),
     "s4g_error_string": (ctypes.c_char_p, [_int]),
     "s4g_workspace_bytes": (_sz, [_int, _i64, _i64, _i64, _i64]),

@@ -10,8 +10,8 @@ Mirror of reference `network_models/models/PointNet2_tcls.py:10-153` (class
 `S4GConfig`.  The module tree reproduces the reference's 200 state_dict
 entries, so `load_checkpoint` accepts a real
 `curvature_model.pth` (`{"model": state_dict}`, optional `module.` prefixes --
-reference `utils/checkpoint.py:31,54-55,81-88`).  Loss / metric classes are
-training-only and out of scope.
+reference `utils/checkpoint.py:31,54-55,81-88`).  The loss / metric classes of
+the three networks are in `losses.py` (`build_loss`).
 
 `ContactPointNet2` mirrors reference `network_models/models/PointNet2.py` (class `PointNet2`, config
 `configs/contact_model.yaml`, whose hyper-parameters equal the curvature model's): 6-D rotation logits turned into
