@@ -93,7 +93,12 @@ extern "C" {
  *     rendered views: the processed cloud and the reference index every view-stage call above starts from);
  *     s4g_eval_view_search_f32 / s4g_eval_view_search_workspace_bytes (the first collision-free placement of every
  *     frame of a view against the view itself) and s4g_eval_scene_grade_f32 / s4g_eval_scene_grade_workspace_bytes
- *     (its ground truth against the dense labelled scene: the data GPD and PointNetGPD are evaluated on). */
+ *     (its ground truth against the dense labelled scene: the data GPD and PointNetGPD are evaluated on);
+ *     s4g_contact_refine_f32 / s4g_contact_refine_workspace_bytes (the per-object frames of s4g_contact_pair_grade_f32
+ *     re-graded over the object's cloud under shifted placements, and the kept rows), s4g_match_knn_f32 (the nearest
+ *     points of every point of a cloud, the indices alone) and s4g_contact_reduce_i32 (the per-point cap of those
+ *     frames with the surplus handed to neighbouring points: the refine and reduce stages between the per-object data
+ *     and the contact model's scenes). */
 #define S4G_ABI_VERSION 14
 
 /* ---------------------------------------------------------------------------
@@ -1152,6 +1157,70 @@ int s4g_contact_select_f32(const int32_t *nearest_bn, const float *cloud_b3n, co
                            const int32_t *valid_bf, const float *search_bf, const float *antipodal_bf, int64_t B,
                            int64_t N, int64_t M, int64_t F, float *normals_b3n, int32_t *best_frame_bn,
                            float *point_score_bn, int32_t *valid_index_bn, int64_t *count_b, s4g_stream_t stream);
+
+/* The refine stage of the contact-object pipeline (csrc/contact_refine.hip; added under ABI 14 with no layout change):
+ * check_single_collision of data_gen/utils/refine_contact_object.py:45-114 for every frame of every object, over the
+ * object's own cloud, without host synchronisation.
+ * g2l (B, F, 4, 4) fp32 row-major; xyz (B, 3, M) fp32; search (B, F) fp32 the frames' search_score.  count_b (device,
+ * may be NULL): the points of object b are its first count_b[b]; frame_count_b (device, may be NULL) likewise for rows.
+ * A row is LIVE when it lies below frame_count_b[b] and search > min_search_score (:46; a NaN is not); other rows are
+ * never scanned and get fail = bit 4 alone.  A live row with a g2l entry that is not finite is never scanned either:
+ * fail = bit 3 alone.
+ * nz, ny, nx in [1, 4], P = nz * ny * nx placements, index (iz * ny + iy) * nx + ix (dz outer, dx inner, :74-83);
+ * params8 (HOST) = {FINGER_LENGTH, BOTTOM_LENGTH, HALF_HAND_THICKNESS, HALF_BOTTOM_WIDTH, HALF_BOTTOM_SPACE, max |dx|,
+ * max |dy|, max |dz|}; tables_2z3y2x (DEVICE) as for s4g_contact_search_f32, and the same inequalities on the same
+ * fp32 local coordinates (:75-85), the sign of dy in y_bool and in |y + dy| the script's:
+ *   finger = count(z & x & y_collision) (:86);  close = count(x & z & y_bool) (:89-90);  behind = count of close points
+ *   with x < 0 (:93).
+ * A frame is kept when every placement has finger <= collision_threshold, close >= min_search_score and behind == 0;
+ * its score is the minimum close count over the placements (:95) as an exact fp32.  1 <= min_search_score < 2^24 and
+ * collision_threshold >= 0 (S4G_EINVAL otherwise): with a minimum of 1 the count gate precedes the min() of an empty
+ * region, where the script raises.  The script returns at the first failing placement; all are counted here.
+ * Outputs: counts_bfp3 int32 (B, F, P, 3) = {finger, close, behind}, zero on rows that are not scanned; kept_bf int32
+ *   (B, F); score_bf fp32 (B, F), 0 where not kept; fail_bf int32 (B, F): bit 0 = finger, bit 1 = too few close
+ *   points, bit 2 = behind, bit 3 = not finite, bit 4 = not live; kept = (fail == 0); kept_index_bf int32 (B, F) the
+ *   kept rows in ascending order, then -1; kept_count_b int64 (B).
+ * Run-to-run bit-identical and batch invariant: integer atomics only.  M, F < 2^30, M >= 1, B <= 65 535.
+ * Workspace: s4g_contact_refine_workspace_bytes(B, M, F, P) bytes (12 per placement); contents need not be
+ * initialised; every launch of the call is a kernel. */
+size_t s4g_contact_refine_workspace_bytes(int64_t B, int64_t M, int64_t F, int64_t P);
+int s4g_contact_refine_f32(const float *g2l_bf44, const float *xyz_b3m, const float *search_bf, int64_t B, int64_t M,
+                           int64_t F, int64_t nz, int64_t ny, int64_t nx, const float *params8,
+                           int32_t min_search_score, int32_t collision_threshold, const float *tables_2z3y2x,
+                           const int64_t *count_b, const int64_t *frame_count_b, int32_t *counts_bfp3,
+                           int32_t *kept_bf, float *score_bf, int32_t *fail_bf, int32_t *kept_index_bf,
+                           int64_t *kept_count_b, void *workspace, size_t workspace_bytes, s4g_stream_t stream);
+
+/* The neighbours of every point of a cloud (csrc/match_normals.hip; added under ABI 14): open3d's
+ * search_hybrid_vector_3d(radius, max_nn) of a cloud's own points as s4g_estimate_normals_f32 runs it -- the live finite
+ * points with fp32 squared distance < radius^2 (strict), of them the max_nn smallest by (squared distance, index), the
+ * point itself included; a lower-index copy of a point therefore ranks before the point -- the indices alone.
+ * cloud (B, 3, N) fp32; live_b int32 (B) or NULL as for s4g_estimate_normals_f32; 1 <= max_nn <= 64.
+ * knn_bnk int32 (B, N, max_nn): the kept indices in rank order, -1 beyond their count; all -1 for a padding row and for
+ * a point that is not finite.  Workspace: what s4g_estimate_normals_workspace_bytes gives for (B, N). */
+int s4g_match_knn_f32(const float *cloud_b3n, const int32_t *live_b, int64_t B, int64_t N, float radius,
+                      int32_t max_nn, int32_t *knn_bnk, void *workspace, size_t workspace_bytes, s4g_stream_t stream);
+
+/* The reduce stage of the contact-object pipeline (csrc/contact_refine.hip; added under ABI 14): the fold of
+ * data_gen/utils/smooth_contact_object.py:61-89, one wave per object.  frame_point_index (B, F) int32; offsets
+ * (B, N + 1) and order (B, F) int32: a CSR whose row i lists, in ascending frame index, the frames that passed the
+ * filter (:37) and whose point is i (:62); knn (B, N, max_nn) from s4g_match_knn_f32; count_b (device, may be NULL) the
+ * points of object b.  Points are visited in ascending index with running counts num[]:
+ *   more than frame_per_point frames: the first frame_per_point - num[i] are appended for i (:64); if more than
+ *     min_rest frames remain beyond the first frame_per_point (:70-71), neighbour n of rank r takes frame rest[r] when
+ *     n < i and num[n] < frame_per_point, or n > i and num[n] < max_neighbor_frame (:75-81); i itself takes nothing;
+ *   1 .. frame_per_point frames: the first min(frame_per_point - num[i], len) are appended (:84).
+ * Outputs in the script's append order: source_frame_bc, point_index_bc int32 (B, cap) -- the frame's row and the point
+ * it now belongs to, the NEIGHBOUR for a spread frame -- then -1; count_out_b int64 (B) stays exact when it exceeds
+ * cap, and flags_b int32 (B) bit 0 says so.  A row of the CSR whose point is outside [0, count) counts for nobody.
+ * 1 <= frame_per_point <= 255, 0 <= max_neighbor_frame <= frame_per_point, 1 <= max_nn <= 8, min_rest >= max_nn - 1
+ * (rest[r] then exists for every rank), 1 <= N <= 65 536 (the running counts are N bytes of LDS), B <= 65 535
+ * (S4G_EINVAL otherwise).  No atomics, no workspace. */
+int s4g_contact_reduce_i32(const int32_t *frame_point_index_bf, const int32_t *offsets_bn1, const int32_t *order_bf,
+                           const int32_t *knn_bnk, const int64_t *count_b, int64_t B, int64_t N, int64_t F,
+                           int32_t frame_per_point, int32_t max_neighbor_frame, int32_t min_rest, int32_t max_nn,
+                           int64_t cap, int32_t *source_frame_bc, int32_t *point_index_bc, int64_t *count_out_b,
+                           int32_t *flags_b, s4g_stream_t stream);
 
 /* The view stage of the curvature model's fast label pipeline (csrc/precomputed_view.hip; added under ABI 14 with no
  * layout change): TorchPrecomputedSingleViewPointCloud.run_score

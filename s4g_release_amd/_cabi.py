@@ -187,6 +187,12 @@ SIGNATURES = {
     "s4g_contact_pair_grade_f32": (_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64,
                                           ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_double), _vp, _i64,
                                           _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "s4g_contact_refine_workspace_bytes": (_sz, [_i64, _i64, _i64, _i64]),
+    "s4g_contact_refine_f32": (_int, [_vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _i64, ctypes.POINTER(ctypes.c_float),
+                                      _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "s4g_match_knn_f32": (_int, [_vp, _vp, _i64, _i64, _f32, _i32, _vp, _vp, _sz, _vp]),
+    "s4g_contact_reduce_i32": (_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i32, _i32, _i32, _i32, _i64, _vp,
+                                      _vp, _vp, _vp, _vp]),
     "s4g_darboux_object_frames_workspace_bytes": (_sz, [_i64, _i64]),
     "s4g_darboux_object_frames_f32": (_int, [_vp, _vp, _vp, _i64, _i64, _f32, _i32, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "s4g_darboux_object_grade_workspace_bytes": (_sz, [_i64, _i64, _i64, _i64, _i64, _i64]),

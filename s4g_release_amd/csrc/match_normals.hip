@@ -692,12 +692,127 @@ __global__ __launch_bounds__(MN_THREADS) void normals_query_kernel(
   flags[(size_t)b * N + q] = flag;
 }
 
+// The neighbour INDICES alone (s4g_match_knn_f32): normals_query_kernel's search over the same build, then the kept
+// list's indices in rank order -- (fp32 squared distance, index) ascending, the query itself or a lower-index copy of
+// it first -- and -1 beyond the count.  A padding row and a point that is not finite have no neighbours.
+__global__ __launch_bounds__(MN_THREADS) void match_knn_kernel(
+    const float* __restrict__ cloud, const int32_t* __restrict__ live, int N, int total, float r2, float inv_h,
+    int max_nn, NormalsWs ws, int32_t* __restrict__ knn) {
+  __shared__ uint64_t lists[MN_WAVES][MN_LIST];
+  const int b = blockIdx.y;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int q = blockIdx.x * MN_WAVES + wave;
+  if (q >= N) return;   // the whole wave
+  const int n_live = normals_live(live, b, N);
+  const float* __restrict__ p0 = cloud + (size_t)b * 3 * N;
+  int32_t* __restrict__ o = knn + ((size_t)b * N + q) * max_nn;
+  float x = 0.f, y = 0.f, z = 0.f;
+  if (q < n_live) { x = p0[q]; y = p0[N + q]; z = p0[2 * (size_t)N + q]; }
+  if (q >= n_live || !(finite(x) && finite(y) && finite(z))) {
+    if (lane < max_nn) o[lane] = -1;
+    return;
+  }
+  MnSelect s;
+  s.list = lists[wave];
+  s.thr = ~0ull;
+  s.n = 0;
+  s.inside = 0;
+  s.max_nn = max_nn;
+  s.lane = lane;
+  const float4 org = ws.origin[b];
+  const bool grid = ws.m.flags[b] == 0 && grid_coord_ok(x, org.x, inv_h) && grid_coord_ok(y, org.y, inv_h) &&
+                    grid_coord_ok(z, org.z, inv_h);
+  if (grid) {
+    const int icx = grid_coord(x, org.x, inv_h), icy = grid_coord(y, org.y, inv_h), icz = grid_coord(z, org.z, inv_h);
+    const int* __restrict__ start = ws.m.start + (size_t)b * MN_CELLS;
+    // lane r < 9 fetches row r's runs, as match_query_kernel does
+    int vb0 = 0, ve0 = 0, vb1 = 0, ve1 = 0;
+    if (lane < 9) {
+      const int dz = lane / 3 - 1, dy = lane % 3 - 1;
+      const int row = mn_cell(0, icy + dy, icz + dz);
+      const int x0 = (icx - 1) & (MN_DIM - 1);
+      vb0 = start[row + x0];
+      if (x0 <= MN_DIM - 3) {
+        ve0 = start[row + x0 + 3];
+      } else {
+        ve0 = start[row + MN_DIM];
+        vb1 = start[row];
+        ve1 = start[row + ((x0 + 3) & (MN_DIM - 1))];
+      }
+    }
+    const float4* __restrict__ rec = ws.m.rec;   // the starts are offsets into the whole chunk
+    for (int r = 0; r < 9; ++r) {
+      for (int run = 0; run < 2; ++run) {
+        int rb = __shfl(run ? vb1 : vb0, r), re = __shfl(run ? ve1 : ve0, r);
+        rb = rb < 0 ? 0 : rb;
+        re = re > total ? total : re;
+        for (int base = rb; base < re; base += 64) {
+          const int i = base + lane;
+          const bool valid = i < re;
+          float4 c = make_float4(0.f, 0.f, 0.f, 0.f);
+          if (valid) c = rec[i];
+          s.consider(valid, dist2<false>(x, y, z, c.x, c.y, c.z), r2, __float_as_int(c.w));
+        }
+      }
+    }
+  } else {
+    for (int base = 0; base < n_live; base += 64) {   // a point that is not finite fails the comparison by itself
+      const int j = base + lane;
+      const bool valid = j < n_live;
+      float cx = 0.f, cy = 0.f, cz = 0.f;
+      if (valid) { cx = p0[j]; cy = p0[N + j]; cz = p0[2 * (size_t)N + j]; }
+      s.consider(valid, dist2<false>(x, y, z, cx, cy, cz), r2, j);
+    }
+  }
+  s.cut();   // ascending, at most max_nn
+  const int k = s.n < max_nn ? s.n : max_nn;
+  if (lane < max_nn) {
+    int32_t j = -1;
+    if (lane < k) {
+      const uint32_t v = (uint32_t)s.list[lane];
+      if (v < (uint32_t)N) j = (int32_t)v;   // (cannot be otherwise: the index is the cloud's own)
+    }
+    o[lane] = j;
+  }
+}
+
 }  // namespace s4g
 
 extern "C" size_t s4g_estimate_normals_workspace_bytes(int64_t B, int64_t N) {
   if (B <= 0 || N <= 0 || N >= (1ll << 30)) return 0;
   return s4g::normals_ws(nullptr, s4g::normals_chunk(B, N), N, nullptr);
 }
+
+namespace s4g {
+
+// The build (clear, origin, keys, sort, scan, order) of scenes [b0, b0 + Bc) that s4g_estimate_normals_f32 and
+// s4g_match_knn_f32 share; the caller launches its query kernel on w.
+static int normals_build(const float* xyz, const int32_t* lv, int64_t Bc, int64_t N, float inv_h, void* workspace,
+                         NormalsWs* w, hipStream_t st) {
+  normals_ws(workspace, Bc, N, w);
+  const size_t n = (size_t)Bc * (size_t)N, cells = (size_t)Bc * MN_CELLS + 1;
+  const size_t n4 = mn_clear_int4(Bc);
+  hipLaunchKernelGGL(match_clear_kernel, dim3((unsigned)((n4 + MN_BUILD_THREADS - 1) / MN_BUILD_THREADS)),
+                     dim3(MN_BUILD_THREADS), 0, st, (int4*)w->m.count, n4);
+  S4G_LAUNCH_CHECK();
+  hipLaunchKernelGGL(normals_origin_kernel, dim3((unsigned)Bc), dim3(MN_BUILD_THREADS), 0, st, xyz, lv, (int)N,
+                     w->origin);
+  S4G_LAUNCH_CHECK();
+  const dim3 bgrid((unsigned)((N + MN_BUILD_THREADS - 1) / MN_BUILD_THREADS), (unsigned)Bc);
+  hipLaunchKernelGGL(normals_keys_kernel, bgrid, dim3(MN_BUILD_THREADS), 0, st, xyz, lv, (int)N, (int)Bc, inv_h, *w);
+  S4G_LAUNCH_CHECK();
+  unsigned bits = MN_CELL_BITS;   // scene numbers 0 .. Bc: Bc itself marks the points no cell holds
+  while (bits < 32 && ((int64_t)1 << (bits - MN_CELL_BITS)) < Bc + 1) ++bits;
+  if (int rc = radix_sort_pairs(w->m.sort, radix_sort_ws_bytes(n), w->m.keys_a, w->m.keys_b, w->m.vals_a, w->m.vals_b,
+                                n, bits, st))
+    return rc;
+  if (int rc = exclusive_scan_i32(w->m.scan, scan_ws_bytes(cells), w->m.count, w->m.start, cells, st)) return rc;
+  hipLaunchKernelGGL(normals_order_kernel, bgrid, dim3(MN_BUILD_THREADS), 0, st, xyz, (int)N, (int)Bc, *w);
+  S4G_LAUNCH_CHECK();
+  return S4G_OK;
+}
+
+}  // namespace s4g
 
 extern "C" int s4g_estimate_normals_f32(const float* cloud_b3n, const float* camera_b3, const int32_t* live_b, int64_t B,
                                         int64_t N, float radius, int32_t max_nn, float* normals_b3n, int32_t* count_bn,
@@ -718,32 +833,45 @@ extern "C" int s4g_estimate_normals_f32(const float* cloud_b3n, const float* cam
   for (int64_t b0 = 0; b0 < B; b0 += chunk) {
     const int64_t Bc = B - b0 < chunk ? B - b0 : chunk;
     NormalsWs w = {};
-    normals_ws(workspace, Bc, N, &w);
-    const size_t n = (size_t)Bc * (size_t)N, cells = (size_t)Bc * MN_CELLS + 1;
     const float* xyz = cloud_b3n + (size_t)b0 * 3 * N;
     const int32_t* lv = live_b ? live_b + b0 : nullptr;
-    const size_t n4 = mn_clear_int4(Bc);
-    hipLaunchKernelGGL(match_clear_kernel, dim3((unsigned)((n4 + MN_BUILD_THREADS - 1) / MN_BUILD_THREADS)),
-                       dim3(MN_BUILD_THREADS), 0, st, (int4*)w.m.count, n4);
-    S4G_LAUNCH_CHECK();
-    hipLaunchKernelGGL(normals_origin_kernel, dim3((unsigned)Bc), dim3(MN_BUILD_THREADS), 0, st, xyz, lv, (int)N,
-                       w.origin);
-    S4G_LAUNCH_CHECK();
-    const dim3 bgrid((unsigned)((N + MN_BUILD_THREADS - 1) / MN_BUILD_THREADS), (unsigned)Bc);
-    hipLaunchKernelGGL(normals_keys_kernel, bgrid, dim3(MN_BUILD_THREADS), 0, st, xyz, lv, (int)N, (int)Bc, inv_h, w);
-    S4G_LAUNCH_CHECK();
-    unsigned bits = MN_CELL_BITS;   // scene numbers 0 .. Bc: Bc itself marks the points no cell holds
-    while (bits < 32 && ((int64_t)1 << (bits - MN_CELL_BITS)) < Bc + 1) ++bits;
-    if (int rc = radix_sort_pairs(w.m.sort, radix_sort_ws_bytes(n), w.m.keys_a, w.m.keys_b, w.m.vals_a, w.m.vals_b, n,
-                                  bits, st))
-      return rc;
-    if (int rc = exclusive_scan_i32(w.m.scan, scan_ws_bytes(cells), w.m.count, w.m.start, cells, st)) return rc;
-    hipLaunchKernelGGL(normals_order_kernel, bgrid, dim3(MN_BUILD_THREADS), 0, st, xyz, (int)N, (int)Bc, w);
-    S4G_LAUNCH_CHECK();
+    if (int rc = normals_build(xyz, lv, Bc, N, inv_h, workspace, &w, st)) return rc;
     const dim3 qgrid((unsigned)((N + MN_WAVES - 1) / MN_WAVES), (unsigned)Bc);
     hipLaunchKernelGGL(normals_query_kernel, qgrid, dim3(MN_THREADS), 0, st, xyz,
-                       camera_b3 ? camera_b3 + (size_t)b0 * 3 : nullptr, lv, (int)N, (int)n, r2, inv_h, (int)max_nn, w,
-                       normals_b3n + (size_t)b0 * 3 * N, count_bn + (size_t)b0 * N, flags_bn + (size_t)b0 * N);
+                       camera_b3 ? camera_b3 + (size_t)b0 * 3 : nullptr, lv, (int)N, (int)(Bc * N), r2, inv_h,
+                       (int)max_nn, w, normals_b3n + (size_t)b0 * 3 * N, count_bn + (size_t)b0 * N,
+                       flags_bn + (size_t)b0 * N);
+    S4G_LAUNCH_CHECK();
+  }
+  return S4G_OK;
+}
+
+// The max_nn nearest points of every point of a cloud within the radius, the indices alone: the kd-tree search of
+// smooth_contact_object.py:72.  Workspace: s4g_estimate_normals_workspace_bytes(B, N).
+extern "C" int s4g_match_knn_f32(const float* cloud_b3n, const int32_t* live_b, int64_t B, int64_t N, float radius,
+                                 int32_t max_nn, int32_t* knn_bnk, void* workspace, size_t workspace_bytes,
+                                 s4g_stream_t stream) {
+  using namespace s4g;
+  if (B < 0 || B > 65535 || N < 0 || N >= (1ll << 30)) return S4G_EINVAL;
+  if (!(radius > 0.f) || !(radius < 1e18f) || max_nn < 1 || max_nn > MN_MAX_NN) return S4G_EINVAL;
+  if (B == 0 || N == 0) return S4G_OK;
+  if (!cloud_b3n || !knn_bnk) return S4G_EINVAL;
+  hipStream_t st = (hipStream_t)stream;
+  const float r2 = radius * radius;
+  const float h = radius * (1.0f + 1.0f / 256.0f);
+  const float inv_h = 1.0f / h;
+  const int64_t chunk = normals_chunk(B, N);
+  const size_t need = normals_ws(nullptr, chunk, N, nullptr);
+  if (!workspace || workspace_bytes < need) return S4G_EWORKSPACE;
+  for (int64_t b0 = 0; b0 < B; b0 += chunk) {
+    const int64_t Bc = B - b0 < chunk ? B - b0 : chunk;
+    NormalsWs w = {};
+    const float* xyz = cloud_b3n + (size_t)b0 * 3 * N;
+    const int32_t* lv = live_b ? live_b + b0 : nullptr;
+    if (int rc = normals_build(xyz, lv, Bc, N, inv_h, workspace, &w, st)) return rc;
+    const dim3 qgrid((unsigned)((N + MN_WAVES - 1) / MN_WAVES), (unsigned)Bc);
+    hipLaunchKernelGGL(match_knn_kernel, qgrid, dim3(MN_THREADS), 0, st, xyz, lv, (int)N, (int)(Bc * N), r2, inv_h,
+                       (int)max_nn, w, knn_bnk + (size_t)b0 * N * max_nn);
     S4G_LAUNCH_CHECK();
   }
   return S4G_OK;

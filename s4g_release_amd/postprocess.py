@@ -3097,3 +3097,6 @@ def label_eval_view(cloud, normals, scene_points, scene_normals, scene_labels, c
     truth = grade_eval_scene_frames(search.global_to_local, scene_points, scene_normals, scene_labels, cfg,
                                     fr.frame_count, taken)
     return EvalViewLabels(fr, search, regions, truth, xyz, normals, scene_points, scene_normals, scene_labels)
+
+
+from .contact_object import *  # noqa: E402,F401,F403  (the refine and reduce stages of the contact-object pipeline)
