@@ -98,7 +98,9 @@ extern "C" {
  *     re-graded over the object's cloud under shifted placements, and the kept rows), s4g_match_knn_f32 (the nearest
  *     points of every point of a cloud, the indices alone) and s4g_contact_reduce_i32 (the per-point cap of those
  *     frames with the surplus handed to neighbouring points: the refine and reduce stages between the per-object data
- *     and the contact model's scenes). */
+ *     and the contact model's scenes); s4g_render_views_f32 / s4g_render_views_workspace_bytes (the rendered views
+ *     themselves: pinhole range images of posed triangle meshes and the noise-free and noisy clouds
+ *     s4g_process_views_f32 and its trace start from). */
 #define S4G_ABI_VERSION 14
 
 /* ---------------------------------------------------------------------------
@@ -1592,6 +1594,42 @@ int s4g_process_views_f32(const float *xyz_b3n, const int32_t *count_b /* may be
                           const float *workspace6, float voxel, const float *origin3, const int32_t *dims3,
                           float radius, int32_t nb_points, float *points_out_b3n, int32_t *index_out_bn,
                           int32_t *counts_out_b3, void *ws, size_t ws_bytes, int flags, s4g_stream_t stream);
+
+/* The rendered views the view stage starts from (csrc/render_views.hip; added under ABI 14 with no layout change):
+ * data_gen/render/cycles_render.py:25-36, 118-153 without Blender -- a pinhole image of RAY LENGTHS per scene and
+ * camera, unprojected along the unit rays of K^-1, cut at a planar depth, z negated and moved to the world frame; the
+ * noisy cloud is the same from range * multiplier on the index set of the noise-free one.  The renderer is pinned by
+ * this restatement alone (Cycles itself cannot be run against it).  B scenes x V cameras in one call; no host read; a
+ * captured call is a plain chain of kernel nodes; run-to-run bit-identical; a scene's result does not depend on the
+ * batch around it.
+ *   tri_bt9 (B, T, 9) fp32 world-space triangles (three vertices, xyz each); tri_count_b (B,) int32 on the device or
+ *   NULL: rows at or past tri_count_b[b] (clamped to [0, T]) do not exist and may hold anything.  cam_bv12 (B, V, 12)
+ *   DOUBLE on the device: the camera-to-world rotation R row-major, then the camera centre c; the camera looks down its
+ *   -z, +x is right, +y is up.  fx, fy, cx, cy: the pinhole; pixel i = row * W + col has x = col + 0.5, y = row + 0.5,
+ *   row 0 is the LOWEST row.  noise_bvp (B, V, H * W) double multipliers of the range, or NULL.
+ * Arithmetic, all in double from the fp32 inputs, each operation rounded once, sums left to right, no FMA:
+ *   camera-frame vertex v = R^T (p - c) (v_i = R_0i d_0 + R_1i d_1 + R_2i d_2); e1 = v1 - v0, e2 = v2 - v0;
+ *   ray r = ((x - cx) / fx, (y - cy) / fy, -1) from the origin, not normalised;
+ *   P = r x e2, det = e1 . P, U = -(v0 . P), Q = -(v0 x e1), V = r . Q, Tn = e2 . Q;
+ *   det > 0: hit iff U >= 0, V >= 0, U + V <= det, Tn > 0; det < 0: the four signs mirrored; det == 0 or a non-finite
+ *   det, U, V or Tn never hits; both faces hit.  Planar depth t = Tn / det; the hit with the smallest t is taken, the
+ *   lowest triangle index among equal t.  nor = sqrt(rx^2 + ry^2 + 1), range32 = (float)(t * nor), dir = (rx / nor,
+ *   ry / nor, 1 / nor).  A pixel is kept iff it was hit and (double)range32 * (1 / nor) < max_depth.  Camera-frame
+ *   point (range32 * dir.x, range32 * dir.y, -(range32 * dir.z)), world point R p + c (row i: R_i0 x + R_i1 y + R_i2 z
+ *   + c_i) rounded to fp32 once; the noisy point the same from (double)range32 * noise.
+ * Dense outputs: range_bvp (B, V, H * W) fp32, +inf on a miss; tri_bvp int32, -1 on a miss.  Compact outputs, the kept
+ * pixels in ascending i: points_bv3p and noisy_bv3p (B, V, 3, H * W) fp32 (noisy_bv3p is not touched when noise_bvp is
+ * NULL), pixel_bvp (B, V, H * W) int32, count_bv (B, V) int32; from count on NaN in the point arrays and -1 in
+ * pixel_bvp (the conventions of s4g_process_views_f32's input and output).
+ * Limits: B * V <= 65 535, 0 < H * W <= 2^22, T < 2^24, fx, fy > 0, all four pinhole values finite (S4G_EINVAL).
+ * Workspace: s4g_render_views_workspace_bytes(B, V, T, H, W) bytes (0 outside the limits; S4G_EWORKSPACE below that),
+ * 256-byte aligned; contents undefined between calls.  Every refusal happens before the first launch. */
+size_t s4g_render_views_workspace_bytes(int64_t B, int64_t V, int64_t T, int64_t H, int64_t W);
+int s4g_render_views_f32(const float *tri_bt9, const int32_t *tri_count_b /* may be NULL */, const double *cam_bv12,
+                         int64_t B, int64_t V, int64_t T, double fx, double fy, double cx, double cy, double max_depth,
+                         int64_t H, int64_t W, const double *noise_bvp /* may be NULL */, float *range_bvp,
+                         int32_t *tri_bvp, float *points_bv3p, float *noisy_bv3p, int32_t *pixel_bvp, int32_t *count_bv,
+                         void *ws, size_t ws_bytes, s4g_stream_t stream);
 
 /* The training objective and metric of the three networks, fused (csrc/loss.hip; added under ABI 14 with no layout
  * change): PointNet2Loss / PointNet2Metric of the reference's network_models/models/PointNet2_tcls.py:156-267

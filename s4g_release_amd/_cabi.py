@@ -215,6 +215,10 @@ SIGNATURES = {
     "s4g_process_views_f32": (_int, [_vp, _vp, _i64, _i64, ctypes.POINTER(ctypes.c_float), _f32,
                                      ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_int32), _f32, _i32, _vp,
                                      _vp, _vp, _vp, _sz, _int, _vp]),
+    "s4g_render_views_workspace_bytes": (_sz, [_i64, _i64, _i64, _i64, _i64]),
+    "s4g_render_views_f32": (_int, [_vp, _vp, _vp, _i64, _i64, _i64, ctypes.c_double, ctypes.c_double, ctypes.c_double,
+                                    ctypes.c_double, ctypes.c_double, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                    _sz, _vp]),
     "s4g_grasp_loss_workspace_bytes": (_sz, [_i64, _i64, _i64]),
     "s4g_grasp_loss_f32": (_int, [ctypes.POINTER(LossDesc), _vp]),
     "s4g_grasp_metric_f32": (_int, [ctypes.POINTER(LossDesc), _vp]),

@@ -3100,3 +3100,4 @@ def label_eval_view(cloud, normals, scene_points, scene_normals, scene_labels, c
 
 
 from .contact_object import *  # noqa: E402,F401,F403  (the refine and reduce stages of the contact-object pipeline)
+from .render import *  # noqa: E402,F401,F403  (the rendered views the view stage starts from)
